@@ -12,7 +12,12 @@ n_gpus = the number of ranks that took part (`ranks_seen`, read back from the RC
 A step = feed_train_data + optimize_parameters of RefGuidedImageCleanModel:
 forward, L1, hand-written backward, gradient all-reduce (N>1), global-norm clip,
 AdamW -- all HIP kernels, fp32, synthetic inputs resident in HBM.
-Prints ONE JSON line (rank 0)."""
+Prints ONE JSON line (rank 0).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the JSON line.  `--full` adds every
+secondary measurement (the per-kernel roofline leg, the exact-fp32 / fast-mode / matcher-active comparison runs, the
+CPU baseline, the N-GPU scale diagnostics).  `--dump-outputs DIR` writes what the last timed step computed as .npy
+files (see dump_outputs)."""
 import argparse
 import json
 import os
@@ -206,6 +211,8 @@ def bench_i2t(a, world, rank, local):
         loss = tr.step(batch)
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, None, loss.item(), tr.params)
     if world > 1:
         t = torch.tensor([dt], device='cuda', dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -246,6 +253,27 @@ def bench_i2t(a, world, rank, local):
                               'note': 'fp32-equivalent FLOPs against the 2-way-split ceiling (833 TF); the Mapper also streams 28 B per '
                                       'trained parameter per step (weights fwd + bwd, gradients, AdamW state)'}}
     print(json.dumps(line), flush=True)
+
+
+DUMP_SAMPLE = 4 << 20         # parameters written by --dump-outputs: all of them up to 4 Mi values (16 MB), else a fixed sample
+
+
+def dump_outputs(out_dir, output, loss, params):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the network output (`output.npy`, float32),
+    the loss (`loss.npy`, float64) and the updated trainable parameters, flattened in named_parameters order (`params.npy`,
+    float32; above DUMP_SAMPLE values a fixed sample: sorted indices drawn with seed 0, the same for every run of one network)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if output is not None:
+        if isinstance(output, (list, tuple)):
+            output = output[-1]
+        np.save(os.path.join(out_dir, 'output.npy'), output.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, 'loss.npy'), np.array([float(loss)], dtype=np.float64))
+    flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, 'params.npy'), flat.cpu().numpy())
 
 
 def pmc_traffic(prefixes):
@@ -350,7 +378,15 @@ def main():
     ap.add_argument('--math', default=None, choices=['bx3', 'f32', 'hx2', 'h1'],
                     help='arithmetic of the dense contractions (default: the library default bx3 -- except the BASELINE configs[4] workload, '
                          '`--arch restormer --size 512 --batch 2`, whose config names fp16 MFMA: h1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the secondary measurements: roofline leg, exact-fp32 / fast-mode / matcher-active runs, CPU baseline, '
+                         'N-GPU scale diagnostics (the --no-* options still drop single legs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the last step\'s output, loss and (a fixed sample of) the updated parameters '
+                         'to DIR/<name>.npy')
     a = ap.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_roofline = a.no_f32_exact = a.no_matcher_active = True
     if a.batch is None:
         a.batch = 8 if a.arch in ('restormer', 'promptir', 'drsformer', 'drsformer_mefc') else 4
     if a.size is None:
@@ -548,6 +584,8 @@ def _main_body(a, world, rank, local, enc):
     barrier()
     dt = time.perf_counter() - t0
     dt_local = dt
+    if a.dump_outputs and rank == 0:     # before any extra step of the --full legs changes the parameters
+        dump_outputs(a.dump_outputs, model.output, model.get_current_log()['l_pix'], model._step_params)
     if world > 1:
         t = torch.tensor([dt], device='cuda', dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -567,7 +605,7 @@ def _main_body(a, world, rank, local, enc):
     # ---- N > 1: what the first real multi-GPU run needs to diagnose itself (it runs on a node this repo's builder never touches):
     # per-rank view of the job, the gradient exchange timed with HIP events on the comm stream, and cross-rank agreement checks
     scale_diag = None
-    if world > 1:
+    if world > 1 and a.full:
         import hashlib
         import socket
         red.timing = []

@@ -1,9 +1,9 @@
 """The outer ring of the drop-in boundary on the CPU: with <repo>/dropin first on sys.path the
 trainer's own import lines (main_train_restoration_with_ref_input.py:10-18) resolve to textualdegremoval_amd without a
 second copy of any module, the model exposes every method the trainer calls (:177-314), EnlargedSampler reproduces
-the reference's index tables (tests/golden/sampler.npz, generated from the reference), and -- in the build
-container, where /root/reference exists -- the UNCHANGED reference trainer script runs on the shims up to the first
-optimize_parameters, which refuses to run without a GPU (no CPU fallback on the product path)."""
+the reference's index tables (tests/golden/sampler.npz, generated from the reference), and a training script's
+sequence of calls (options -> experiment folders -> dataset -> loader -> model -> step) runs on the shims up to the
+first optimize_parameters, which refuses to run without a GPU (no CPU fallback on the product path)."""
 import os
 import subprocess
 import sys
@@ -13,7 +13,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'dropin'), ROOT]), HIP_VISIBLE_DEVICES='')
-REF_TRAINER = '/root/reference/scripts/train/main_train_restoration_with_ref_input.py'
 
 IMPORT_LINES = '''
 from data import create_dataloader, create_dataset
@@ -69,16 +68,41 @@ def test_enlarged_sampler_matches_reference_index_tables(golden_dir):
         assert counts.sum() == total and counts.max() - counts.min() <= 1
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TRAINER), reason='the reference checkout only exists in the build container')
-def test_unchanged_reference_trainer_runs_on_the_shims_until_the_gpu_step(tmp_path):
+# A training script's path through the shims, written here (the reference's own trainer script is not part of this
+# repository): options file -> experiment folders -> logger -> dataset / sampler / loader -> model -> first step, every
+# module imported through the trainer's own import lines.  Without a GPU the step must refuse to run.
+TRAIN_DRIVER = IMPORT_LINES + '''
+import logging
+import os
+import sys
+opt = parse(sys.argv[1], is_train=True)
+opt['dist'] = False
+opt['rank'], opt['world_size'] = get_dist_info()
+make_exp_dirs(opt)
+logger = get_root_logger(logger_name='basicsr', log_level=logging.INFO, log_file=os.path.join(opt['path']['log'], 'train.log'))
+logger.info(dict2str(opt))
+set_random_seed(opt['manual_seed'])
+ds_opt = opt['datasets']['train']
+train_set = create_dataset(ds_opt)
+sampler = EnlargedSampler(train_set, opt['world_size'], opt['rank'], ds_opt['dataset_enlarge_ratio'])
+loader = create_dataloader(train_set, ds_opt, num_gpu=opt['num_gpu'], dist=opt['dist'], sampler=sampler, seed=opt['manual_seed'])
+model = create_model(opt)
+batch = CPUPrefetcher(loader).next()
+assert batch['lq'].shape == (2, 3, 128, 128) and batch['ref'].shape == (2, 3, 128, 128), {k: v.shape for k, v in batch.items()}
+model.update_learning_rate(1, warmup_iter=opt['train'].get('warmup_iter', -1))
+model.feed_train_data(batch)
+model.optimize_parameters(1)
+'''
+
+
+def test_training_script_runs_on_the_shims_until_the_gpu_step(tmp_path):
     yml = open(os.path.join(ROOT, 'tests', 'data', 'train_nafnet_ref_synthetic_debug.yml')).read().replace('num_gpu: 1', 'num_gpu: 0')
     p = tmp_path / 'cpu.yml'
     p.write_text(yml)
-    out = subprocess.run([sys.executable, REF_TRAINER, '-opt', str(p)], capture_output=True, text=True, cwd=str(tmp_path),
+    out = subprocess.run([sys.executable, '-c', TRAIN_DRIVER, str(p)], capture_output=True, text=True, cwd=str(tmp_path),
                          env=dict(ENV, TDR_EXPERIMENTS_ROOT=str(tmp_path)), timeout=300)
     log = out.stdout + out.stderr
-    assert 'Dataset Dataset_SyntheticPairedWithRef - TrainSet is created.' in log
-    assert 'Network: NAFNetRefFusion, with parameters: 1,409,867' in log
-    assert 'Start training from epoch: 0, iter: 0' in log
-    assert 'model.optimize_parameters(current_iter)' in log and 'NotImplementedError: HIP step needs a GPU' in log
+    assert 'Dataset Dataset_SyntheticPairedWithRef - TrainSet is created.' in log, log[-3000:]
+    assert 'Network: NAFNetRefFusion, with parameters: 1,409,867' in log, log[-3000:]
+    assert out.returncode != 0 and 'in optimize_parameters' in log and 'NotImplementedError: HIP step needs a GPU' in log, log[-3000:]
     assert os.path.isdir(tmp_path / 'experiments' / 'debug_nafnet_ref_synthetic' / 'models')

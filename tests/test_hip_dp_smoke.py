@@ -22,7 +22,7 @@ def _bench(nproc, port, wrap):
                 '--master-port', str(port)]
     cmd += [os.path.join(ROOT, 'bench.py'), '--gpus', str(nproc), '--steps', '2', '--warmup', '1', '--width', '8', '--enc', '1,1,1,1',
             '--size', '128', '--batch', '1', '--backend', 'gloo', '--bucket-mb', '0.25',
-            '--no-cpu-baseline']     # roofline leg on: every rank must run its instrumented step
+            '--full', '--no-cpu-baseline']     # roofline leg and scale diagnostics on: every rank must run its instrumented step
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -232,7 +232,7 @@ def _teacher_forced(mode, net, traj, data):
         named = dict(model.net_g.named_parameters())
         assert set(named) == set(traj[0][0]), 'the mirror and the oracle name the same parameters'
         opt = model.optimizer_g
-        rel_l2, rel_max, loss_d, worst = [], [], [], ('', 0.0)
+        rel_l2, rel_max, loss_d, loss_h, worst = [], [], [], [], ('', 0.0)
         for it, (before, m_or, v_or, l_or, after) in enumerate(traj, start=1):
             t = it - 1
             # ---- teacher forcing: parameters, both moments and the step count of the oracle, in place (the captured graph keeps its pointers)
@@ -265,10 +265,19 @@ def _teacher_forced(mode, net, traj, data):
             rel_l2.append(math.sqrt(num / max(den, 1e-300)))
             rel_max.append(mx)
             loss_d.append(abs(l_hip - l_or))
+            loss_h.append(l_hip)
             assert opt.guard is None or int(opt.guard.read().step) == it
-        return dict(rel_l2=rel_l2, rel_max=rel_max, loss_diff=loss_d, worst=worst)
+        return dict(rel_l2=rel_l2, rel_max=rel_max, loss_diff=loss_d, loss=loss_h, worst=worst)
     finally:
         K.set_math(prev)
+
+
+def _oracle_loss_f64(cfg, P, pair):
+    """the oracle's forward + L1 of one step in float64: the arbiter where the fp32 oracle sits on a near-tie of a discrete decision"""
+    lq, gt, ref = pair
+    with torch.no_grad():
+        out = O.nafnet_ref_forward({k: v.double() for k, v in P.items()}, cfg, lq.double(), ref.double())
+        return float(O.l1_loss(out, gt.double()))
 
 
 def test_teacher_forced_300_steps_w8_128():
@@ -278,7 +287,10 @@ def test_teacher_forced_300_steps_w8_128():
     lr * m_hat / (sqrt(v_hat) + eps) has amplified a 1e-7 gradient difference on elements with small second moments.  About 1 step in 100
     sits at 1e-3 in both arithmetics: a single discrete decision of the step (a ReLU unit of the MASA encoder or a near-tie of its arg-max)
     resolved the other way, which moves one bias row -- the same events the full-size tests count and force.  Bars:
-      * loss of the step: |hip - oracle| <= 2e-6 at every step (same weights, same data: only the forward arithmetic differs);
+      * loss of the step: |hip - oracle| <= 2e-6 at every step (same weights, same data: only the forward arithmetic differs).  A forward
+        decision (the arg-max of the MASA match) that sits on a near-tie can fall the other way in the fp32 oracle than on the device, which
+        moves the loss by ~1e-6 in BOTH device arithmetics at once: at such a step (at most 1 in 100) the same oracle forward in float64
+        decides, and the device loss must lie within 2e-6 of THAT;
       * update distance: median <= 3e-5, 90th percentile <= 5e-5, and the default arithmetic's median within 20 % (+ 2e-6) of exact fp32's --
         a biased product scheme would shift the whole distribution, not its tail;
       * decision-flip steps (distance > 2e-4; two boxes: 3 / 10 of 300 in exact fp32, 4 / 12 in the default arithmetic, the largest 1.5e-3 ... 2e-2
@@ -303,7 +315,15 @@ def test_teacher_forced_300_steps_w8_128():
               f'worst {max(r["rel_max"]):.3e} ({r["worst"][0]}); loss max diff {max(r["loss_diff"]):.3e}')
     def pct(v, q):
         return sorted(v)[min(int(len(v) * q), len(v) - 1)]
-    assert max(b['loss_diff']) <= 2e-6, max(b['loss_diff'])
+    off = sorted({i for r in res.values() for i, v in enumerate(r['loss_diff']) if v > 2e-6})
+    assert len(off) <= 0.01 * steps, [(i, f['loss_diff'][i], b['loss_diff'][i]) for i in off]
+    l64 = {i: _oracle_loss_f64(cfg, traj[i][0], data[i % len(data)]) for i in off}
+    for i in off:
+        print(f'   step {i + 1}: |hip - oracle fp32| f32 {f["loss_diff"][i]:.3e} bx3 {b["loss_diff"][i]:.3e}; '
+              f'|hip - oracle fp64| f32 {abs(f["loss"][i] - l64[i]):.3e} bx3 {abs(b["loss"][i] - l64[i]):.3e}')
+    for m, r in res.items():
+        bad = [(i, r['loss_diff'][i], abs(r['loss'][i] - l64[i])) for i in off if r['loss_diff'][i] > 2e-6 and abs(r['loss'][i] - l64[i]) > 2e-6]
+        assert not bad, (m, bad)
     for m, r in res.items():
         assert pct(r['rel_l2'], 0.5) <= 3e-5 and pct(r['rel_l2'], 0.9) <= 5e-5, (m, pct(r['rel_l2'], 0.5), pct(r['rel_l2'], 0.9))
         flips = [v for v in r['rel_l2'] if v > 2e-4]
