@@ -21,9 +21,10 @@ extern "C" {
 #endif
 
 /* C-ABI version: bumped with every incompatible change of this header (100 rounds 1-2, 101 round 3, 102 round 4, 103 - 104
- * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions); the
+ * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
+ * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*); the
  * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
-#define TDR_ABI_VERSION 107
+#define TDR_ABI_VERSION 108
 int tdr_version(void);
 const char* tdr_last_error(void);
 
@@ -892,6 +893,40 @@ int tdr_sf_local_affine(const float* x, int64_t x_ns, const float* m, const floa
                         float* y, int64_t y_ns, void* stream);
 int tdr_sf_emerge(const float* x, int64_t x_ns, const float* low, int N, int C, int HW, float* out, void* stream);
 int tdr_sf_softmax_mix(const float* x, int64_t x_ns, const float* low, const float* lh, const float* ll, int N, int C, int HW, float* mix, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * NAFNetDynamicFusion (models/archs/network_nafnet_guided_diffir_arch.py:250-375): the text-embedding modulation of every block
+ * (csrc/tdr_dynfusion.hip, ABI 108).  The convolutions, LayerNorm backward and depthwise conv run on the entry points above.
+ * --------------------------------------------------------------------------- */
+/* The embedding projections of ALL blocks (`kernel`, `sg1.kernel`, `sg2.kernel`: Linear(K = 10 * 1024, rows, bias=False) on the flattened
+ * k_v [N][K]) as one table in DEVICE memory: 4 int64 words per weight {W, col0, rows, tile0}, tile0 = sum of ceil(rows' / R) over the
+ * weights before it, R = tdr_kvproj_tile_rows(); ntiles = the total.  out [N][ld]: out[n][col0 + r] = sum_k W[r][k] kv[n][k] -- every weight
+ * element read once for all N <= 16 images, fp32 FMA in a fixed order.
+ * wgrad: gtable [nseg] int64 = the weight-gradient buffers; dW[r][k] = sum_n dk[n][col0 + r] kv[n][k], each element written once.
+ * dkv: dkv[n][k] = sum over all weights and rows of dk[n][col0 + r] W[r][k], two fixed-order stages through
+ *   ws (tdr_kvproj_dkv_ws_floats floats). */
+int tdr_kvproj_tile_rows(void);
+int tdr_kvproj_fwd(const void* table, int nseg, int64_t ntiles, const float* kv, int N, int K, float* out, int64_t ld, void* stream);
+int tdr_kvproj_wgrad(const void* table, const void* gtable, int nseg, int64_t ntiles, const float* kv, const float* dk, int64_t ld, int N,
+                     int K, void* stream);
+int tdr_kvproj_dkv_parts(int64_t ntiles);
+int64_t tdr_kvproj_dkv_ws_floats(int64_t ntiles, int N, int K);
+int tdr_kvproj_dkv(const void* table, int nseg, int64_t ntiles, const float* dk, int64_t ld, int N, int K, float* dkv, float* ws,
+                   void* stream);
+/* Per-(image, channel) affines; a, b (and da, db) are [N][*] rows with image strides ab_ns (d_ns) -- slices of the projection output.
+ * modln_fwd: LayerNorm2d of m = x a + b (x dense [N][C][HW]), mu / rstd [N][HW] those of m (for tdr_layernorm2d_bwd on the recomputed m);
+ * nc_affine: y = x a + b;  nc_affine_bwd: dx = a dm (+ add, may be NULL), da = sum_hw dm x, db = sum_hw dm;
+ * modgate_fwd: t [N][2c][HW], u = t a + b (2c channels), g [N][c][HW] = u[:c] u[c:], pooled [N][c] = mean g (may be NULL);
+ * modgate_bwd: d = dg + dgb[n][j] dgb_mul (dgb may be NULL) -> dt [N][2c][HW], da / db over the 2c channels. */
+int tdr_modln_fwd(const float* x, const float* a, const float* b, int64_t ab_ns, const float* w, const float* lb, float eps, int N, int C,
+                  int HW, float* y, float* mu, float* rstd, void* stream);
+int tdr_nc_affine(const float* x, const float* a, const float* b, int64_t ab_ns, int N, int C, int HW, float* y, void* stream);
+int tdr_nc_affine_bwd(const float* dm, const float* x, const float* a, int64_t ab_ns, const float* add, int N, int C, int HW, float* dx,
+                      float* da, float* db, int64_t d_ns, void* stream);
+int tdr_modgate_fwd(const float* t, const float* a, const float* b, int64_t ab_ns, int N, int c, int HW, float* g, float* pooled,
+                    void* stream);
+int tdr_modgate_bwd(const float* dg, const float* dgb, float dgb_mul, const float* t, const float* a, const float* b, int64_t ab_ns, int N,
+                    int c, int HW, float* dt, float* da, float* db, int64_t d_ns, void* stream);
 
 #ifdef __cplusplus
 }

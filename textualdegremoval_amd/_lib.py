@@ -15,7 +15,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TDR_LIB_PATH', os.path.join(_HERE, 'libtdr_hip.so'))   # override: profiling probe builds
 
-ABI_VERSION = 107      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
+ABI_VERSION = 108      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
 c_fp = C.c_void_p      # device pointers travel as integers
 i32, i64, f32 = C.c_int, C.c_int64, C.c_float
 
@@ -332,6 +332,17 @@ SIGNATURES = {
     'tdr_multi_copy_guarded': (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, i32, c_fp, c_fp]),
     'tdr_grad_sumsq_guarded': (i32, [c_fp] * 5 + [i32, c_fp, c_fp, c_fp, f32, f32, c_fp]),
     'tdr_adamw_step_guarded': (i32, [c_fp] * 8 + [i32, c_fp, c_fp, c_fp, f32, i32, i32, f32, f32, f32, f32, c_fp]),
+    'tdr_kvproj_tile_rows': (i32, []),
+    'tdr_kvproj_fwd': (i32, [c_fp, i32, i64, c_fp, i32, i32, c_fp, i64, c_fp]),
+    'tdr_kvproj_wgrad': (i32, [c_fp, c_fp, i32, i64, c_fp, c_fp, i64, i32, i32, c_fp]),
+    'tdr_kvproj_dkv_parts': (i32, [i64]),
+    'tdr_kvproj_dkv_ws_floats': (i64, [i64, i32, i32]),
+    'tdr_kvproj_dkv': (i32, [c_fp, i32, i64, c_fp, i64, i32, i32, c_fp, c_fp, c_fp]),
+    'tdr_modln_fwd': (i32, [c_fp, c_fp, c_fp, i64, c_fp, c_fp, f32, i32, i32, i32, c_fp, c_fp, c_fp, c_fp]),
+    'tdr_nc_affine': (i32, [c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp]),
+    'tdr_nc_affine_bwd': (i32, [c_fp, c_fp, c_fp, i64, c_fp, i32, i32, i32, c_fp, c_fp, c_fp, i64, c_fp]),
+    'tdr_modgate_fwd': (i32, [c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp, c_fp]),
+    'tdr_modgate_bwd': (i32, [c_fp, c_fp, f32, c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp, c_fp, i64, c_fp]),
 }
 
 _lib = None

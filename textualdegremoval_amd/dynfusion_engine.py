@@ -1,0 +1,254 @@
+"""NAFNetDynamicFusion forward/backward on the HIP kernels (models/archs/network_nafnet_guided_diffir_arch.py:250-375, :445-544).
+
+The U-Net of engine.unet_fwd / unet_bwd with every block conditioned on the textual embedding k_v [N, 10, 1024]: per block of width c
+the projections `kernel` (2c outputs), `sg1.kernel` (4c) and `sg2.kernel` (4c) of the flattened k_v give per-(image, channel) affines
+
+    m = x a0 + b0 -> norm1 -> conv1 -> dw3x3 -> u = dw a1 + b1 ; g = u[:c] u[c:] -> SCA -> conv3 ; y = x + (.) beta
+    v = conv4(norm2(y)) a2 + b2 ; h = v[:c] v[c:] -> conv5 ; out = y + (.) gamma
+
+All projections of the network run as ONE launch (csrc/tdr_dynfusion.hip, tdr_kvproj_fwd) into one [N, sum 10c] tensor; the blocks
+read their slices.  The blocks run the per-op launches of engine.naf_fwd / naf_bwd (the fused head / tail chains are not extended)
+plus the modulation kernels.  sg2's gate is materialised (`h`) and conv5 runs ungated on it.  No ATen arithmetic runs on
+the device: torch only allocates and views memory.
+"""
+import torch
+
+from . import engine as E
+from . import kernels as K
+from .kernels import PACK_DGRAD_S1, PACK_FWD
+
+KV_DIM = 10 * 1024          # in_features of every projection (`nn.Linear(10 * 1024, ., bias=False)`, :257, :305)
+
+
+def block_prefixes(cfg):
+    """the blocks in forward order, with their widths: [(prefix, c)]"""
+    out, chan = [], cfg['width']
+    for lvl, n in enumerate(cfg['enc_blk_nums']):
+        out += [(f'encoders.{lvl}.layers.{j}.', chan) for j in range(n)]
+        chan *= 2
+    out += [(f'middle_blks.layers.{j}.', chan) for j in range(cfg['middle_blk_num'])]
+    for lvl, n in enumerate(cfg['dec_blk_nums']):
+        chan //= 2
+        out += [(f'decoders.{lvl}.layers.{j}.', chan) for j in range(n)]
+    return out
+
+
+PROJ_SUFFIXES = ('kernel.0.weight', 'sg1.kernel.0.weight', 'sg2.kernel.0.weight')
+
+
+def proj_names(pre):
+    return tuple(pre + s for s in PROJ_SUFFIXES)
+
+
+class ProjTable:
+    """the segment table of tdr_kvproj_*: one row {W, col0, rows, tile0} per projection weight, in block order.
+    offs[prefix] = the block's first column of the projection output ([a0 | b0 | a1 | b1 | a2 | b2] = c, c, 2c, 2c, 2c, 2c)."""
+
+    def __init__(self, P, blocks, device):
+        R = K._lib.load().tdr_kvproj_tile_rows()
+        rows, self.offs, self.weights, self.shapes = [], {}, [], []
+        col = tile = 0
+        for pre, c in blocks:
+            self.offs[pre] = col
+            for name, n in zip(proj_names(pre), (2 * c, 4 * c, 4 * c)):
+                w = P[name]
+                assert w.shape == (n, KV_DIM) and w.is_contiguous() and w.dtype == torch.float32
+                rows.append((w.data_ptr(), col, n, tile))
+                self.weights.append(name)
+                self.shapes.append(torch.Size((n, KV_DIM)))
+                col += n
+                tile += -(-n // R)
+        self.ld, self.ntiles, self.nseg = col, tile, len(rows)
+        self.tab = torch.tensor(rows, dtype=torch.int64).to(device)
+        self.key = tuple(r[0] for r in rows)
+
+
+_tables = {}
+
+
+def proj_table(P, blocks, device):
+    """blocks = [(prefix, c)]; cached per set of weight buffers (the optimiser updates them in place)"""
+    names = [n for pre, _ in blocks for n in proj_names(pre)]
+    key = (str(device),) + tuple(P[n].data_ptr() for n in names)
+    t = _tables.get(key)
+    if t is None:
+        if len(_tables) > 64:
+            _tables.clear()
+        t = _tables[key] = ProjTable(P, blocks, device)
+    return t
+
+
+def proj_fwd(P, blocks, kvf):
+    """every projection of `blocks` in one launch -> (table, Kt [N, sum 10c])"""
+    tab = proj_table(P, blocks, kvf.device)
+    return tab, K.kvproj_fwd(tab.tab, tab.nseg, tab.ntiles, kvf, tab.ld)
+
+
+def proj_bwd(tab, kvf, dK, G, need_dkv):
+    """every projection weight gradient in one launch (into G), then the gradient of k_v [N, 10240] when asked for"""
+    grads = [torch.empty(sh, dtype=torch.float32, device=kvf.device) for sh in tab.shapes]
+    gtab = torch.tensor([t.data_ptr() for t in grads], dtype=torch.int64).to(kvf.device)
+    K.kvproj_wgrad(tab.tab, gtab, tab.nseg, tab.ntiles, kvf, dK)
+    for n, t in zip(tab.weights, grads):
+        G[n] = t
+    return K.kvproj_dkv(tab.tab, tab.nseg, tab.ntiles, dK, kvf.shape[1]) if need_dkv else None
+
+
+def _slices(Kt, off, c):
+    """(a0, b0, a1, b1, a2, b2) row slices of one block"""
+    return (Kt[:, off:off + c], Kt[:, off + c:off + 2 * c], Kt[:, off + 2 * c:off + 4 * c], Kt[:, off + 4 * c:off + 6 * c],
+            Kt[:, off + 6 * c:off + 8 * c], Kt[:, off + 8 * c:off + 10 * c])
+
+
+def dyn_naf_fwd(x, P, Kt, off):
+    """NAFBlock_DynamicFusion.forward (:350-375) on x [N,c,H,W] with the block's projection slices of Kt"""
+    N, c, H, W = x.shape
+    a0, b0, a1, b1, a2, b2 = _slices(Kt, off, c)
+    xn, mu1, rs1 = K.modln_fwd(x, a0, b0, P['norm1.weight'], P['norm1.bias'], E.LN_EPS)
+    wp, mp, *_ = K.pack_weights(P['conv1.weight'], PACK_FWD)
+    t1 = K.conv_forward(xn, wp, mp, 2 * c, 1, bias=P['conv1.bias'])
+    d2 = K.dwk_fwd(t1, P['conv2.weight'], P['conv2.bias'])
+    g, pooled = K.modgate_fwd(d2, a1, b1, want_pool=True)
+    s = K.sca_fwd(pooled, P['sca.1.weight'], P['sca.1.bias'])
+    wp, mp, *_ = K.pack_weights(P['conv3.weight'], PACK_FWD)
+    y = K.conv_forward(g, wp, mp, c, 1, kscale=s, bias=P['conv3.bias'], scale=P['beta'].view(-1), res=x)
+    yn, mu2, rs2 = K.layernorm2d_fwd(y, P['norm2.weight'], P['norm2.bias'], E.LN_EPS)
+    wp, mp, *_ = K.pack_weights(P['conv4.weight'], PACK_FWD)
+    t4 = K.conv_forward(yn, wp, mp, 2 * c, 1, bias=P['conv4.bias'])
+    h, _ = K.modgate_fwd(t4, a2, b2)
+    wp, mp, *_ = K.pack_weights(P['conv5.weight'], PACK_FWD)
+    out = K.conv_forward(h, wp, mp, c, 1, bias=P['conv5.bias'], scale=P['gamma'].view(-1), res=y)
+    return out, (x, xn, mu1, rs1, t1, d2, g, pooled, s, y, yn, mu2, rs2, t4, h, off)
+
+
+def dyn_naf_bwd(dout, P, saved, Kt, dK):
+    """-> (dx, G); the gradients of the block's projection outputs go to its columns of dK"""
+    x, xn, mu1, rs1, t1, d2, g, pooled, s, y, yn, mu2, rs2, t4, h, off = saved
+    N, c, H, W = x.shape
+    a0, b0, a1, b1, a2, b2 = _slices(Kt, off, c)
+    da0, db0, da1, db1, da2, db2 = _slices(dK, off, c)
+    beta, gamma = P['beta'].view(-1), P['gamma'].view(-1)
+    G = {}
+    dout = dout.contiguous()
+    # ---- conv5 (+ gamma) on the materialised gate h
+    G5, S5 = K.conv_wgrad(h, dout, c, c, 1, want_db=True)
+    dw5, db5, dgam = K.scaled_conv_param_grads(G5.view(c, c), S5, P['conv5.weight'], P['conv5.bias'], gamma)
+    G['conv5.weight'], G['conv5.bias'], G['gamma'] = dw5.view(c, c, 1, 1), db5, dgam.view(1, c, 1, 1)
+    wp, mp, *_ = K.pack_weights(P['conv5.weight'], PACK_DGRAD_S1)
+    dh = K.conv_forward(dout, wp, mp, c, 1, kscale=gamma)
+    # ---- sg2 -> conv4 -> norm2 (+ the residual branch of `y + x * gamma`)
+    dt4 = K.modgate_bwd(dh, t4, a2, b2, da2, db2)
+    g4, b4 = K.conv_wgrad(yn, dt4, 2 * c, c, 1, want_db=True)
+    G['conv4.weight'], G['conv4.bias'] = g4.view(2 * c, c, 1, 1), b4
+    wp, mp, *_ = K.pack_weights(P['conv4.weight'], PACK_DGRAD_S1)
+    dyn = K.conv_forward(dt4, wp, mp, c, 1)
+    dy, G['norm2.weight'], G['norm2.bias'] = K.layernorm2d_bwd(dyn, y, mu2, rs2, P['norm2.weight'], add=dout)
+    # ---- conv3 / SCA / beta
+    G3, S3 = K.conv_wgrad(g, dy, c, c, 1, per_image=True, want_db=True)
+    dw3, db3, dbeta, dwsca, dbsca, dpooled = K.sca_bwd(G3, S3, P['conv3.weight'], P['conv3.bias'], beta, s, pooled, P['sca.1.weight'])
+    G['conv3.weight'], G['conv3.bias'], G['beta'] = dw3, db3, dbeta
+    G['sca.1.weight'], G['sca.1.bias'] = dwsca, dbsca
+    wp, mp, *_ = K.pack_weights(P['conv3.weight'], PACK_DGRAD_S1)
+    dg = K.conv_forward(dy, wp, mp, c, 1, kscale=beta, scale=s, bias2=dpooled, bias2_mul=1.0 / (H * W))
+    # ---- sg1 -> depthwise conv2
+    dd2 = K.modgate_bwd(dg, d2, a1, b1, da1, db1)
+    dt1, G['conv2.weight'], G['conv2.bias'] = K.dwk_bwd(dd2, None, t1, P['conv2.weight'], want_db=True)
+    # ---- conv1 -> norm1 (input recomputed) -> the modulation x a0 + b0 (+ dy)
+    g1, b1g = K.conv_wgrad(xn, dt1, 2 * c, c, 1, want_db=True)
+    G['conv1.weight'], G['conv1.bias'] = g1.view(2 * c, c, 1, 1), b1g
+    wp, mp, *_ = K.pack_weights(P['conv1.weight'], PACK_DGRAD_S1)
+    dxn = K.conv_forward(dt1, wp, mp, c, 1)
+    m = K.nc_affine(x, a0, b0)
+    dm, G['norm1.weight'], G['norm1.bias'] = K.layernorm2d_bwd(dxn, m, mu1, rs1, P['norm1.weight'])
+    dx = K.nc_affine_bwd(dm, x, a0, da0, db0, add=dy)
+    return dx, G
+
+
+def _seq_fwd(x, P, pre, n, Kt, tab):
+    saved = []
+    for i in range(n):
+        bp = f'{pre}{i}.'
+        x, sv = dyn_naf_fwd(x, E._sub(P, bp), Kt, tab.offs[bp])
+        saved.append(sv)
+    return x, saved
+
+
+def _seq_bwd(d, P, pre, n, saved, Kt, dK, G):
+    for i in reversed(range(n)):
+        bp = f'{pre}{i}.'
+        d, g = dyn_naf_bwd(d, E._sub(P, bp), saved[i], Kt, dK)
+        E._put(G, bp, g)
+    return d
+
+
+def flat_kv(kv, N):
+    """k_v [N, 10, 1024] -> [N, 10240] (torch.flatten(k_v, start_dim=1), :353); a different feature count fails as the reference's
+    Linear does (defect R10: a Mapper(num_words=20) embedding)"""
+    kvf = kv.reshape(kv.shape[0], -1)
+    if kvf.shape[1] != KV_DIM:
+        raise RuntimeError(f'mat1 and mat2 shapes cannot be multiplied ({kvf.shape[0]}x{kvf.shape[1]} and {KV_DIM}x(.)): '
+                           f'NAFNetDynamicFusion projects k_v flattened to 10 x 1024 features')
+    if kvf.shape[0] != N:
+        raise ValueError(f'k_v has batch {kvf.shape[0]}, the image batch is {N}')
+    if N > 16:
+        raise NotImplementedError('NAFNetDynamicFusion on the HIP path: at most 16 images per call (the projection kernels keep one '
+                                  'accumulator per image)')
+    return kvf.contiguous()
+
+
+def dyn_unet_fwd(P, cfg, inp, kv):
+    """NAFNetDynamicFusion.forward (:512-536) -> (out, saved)"""
+    n_enc = len(cfg['enc_blk_nums'])
+    N, _, H0, W0 = inp.shape
+    kvf = flat_kv(kv, N)
+    tab, Kt = proj_fwd(P, block_prefixes(cfg), kvf)
+    mult = 1 << n_enc
+    Hp, Wp = -(-H0 // mult) * mult, -(-W0 // mult) * mult
+    inp_p = inp.contiguous() if (Hp, Wp) == (H0, W0) else K.pad_crop(inp.contiguous(), Hp, Wp)
+    x = E.conv_fwd(inp_p, P['intro.weight'], P['intro.bias'], 1, 1)
+    sv_levels, skips = [], []
+    for lvl in range(n_enc):
+        x, sv_e = _seq_fwd(x, P, f'encoders.{lvl}.layers.', cfg['enc_blk_nums'][lvl], Kt, tab)
+        skips.append(x)
+        sv_levels.append((sv_e, x))
+        x = E.conv_fwd(x, P[f'downs.{lvl}.weight'], P[f'downs.{lvl}.bias'], 2, 0)
+    x, sv_m = _seq_fwd(x, P, 'middle_blks.layers.', cfg['middle_blk_num'], Kt, tab)
+    sv_dec = []
+    for lvl in range(len(cfg['dec_blk_nums'])):
+        xin = x
+        x = E.up_fwd(xin, P[f'ups.{lvl}.0.weight'], skips[-1 - lvl])
+        x, sv_d = _seq_fwd(x, P, f'decoders.{lvl}.layers.', cfg['dec_blk_nums'][lvl], Kt, tab)
+        sv_dec.append((xin, sv_d))
+    out_p = E.conv_fwd(x, P['ending.weight'], P['ending.bias'], 1, 1, res=inp_p)
+    out = out_p if (Hp, Wp) == (H0, W0) else K.pad_crop(out_p, H0, W0)
+    return out, ((H0, W0, Hp, Wp), inp_p, sv_levels, sv_m, sv_dec, x, kvf, Kt, tab)
+
+
+def dyn_unet_bwd(dout, P, cfg, saved, need_dkv=True, G=None):
+    """-> (dinp, dkv or None, G, dK): gradients w.r.t. the image, k_v (shape [N, 10240]), every parameter, and the projection outputs"""
+    with E.deferred_join():
+        (H0, W0, Hp, Wp), inp_p, sv_levels, sv_m, sv_dec, xe, kvf, Kt, tab = saved
+        n_enc = len(cfg['enc_blk_nums'])
+        G = {} if G is None else G
+        dK = torch.empty_like(Kt)            # every column is written by exactly one block's reductions
+        dout = dout.contiguous()
+        if (Hp, Wp) != (H0, W0):
+            dout = K.pad_crop(dout, Hp, Wp)
+        d, G['ending.weight'], G['ending.bias'] = E.conv_bwd(dout, xe, P['ending.weight'], 1, 1)
+        dskips = [None] * n_enc
+        for lvl in reversed(range(len(cfg['dec_blk_nums']))):
+            xin, sv_d = sv_dec[lvl]
+            d = _seq_bwd(d, P, f'decoders.{lvl}.layers.', cfg['dec_blk_nums'][lvl], sv_d, Kt, dK, G)
+            dskips[n_enc - 1 - lvl] = d
+            d, G[f'ups.{lvl}.0.weight'] = E.up_bwd(d, xin, P[f'ups.{lvl}.0.weight'])
+        d = _seq_bwd(d, P, 'middle_blks.layers.', cfg['middle_blk_num'], sv_m, Kt, dK, G)
+        for lvl in reversed(range(n_enc)):
+            sv_e, x_skip = sv_levels[lvl]
+            d, G[f'downs.{lvl}.weight'], G[f'downs.{lvl}.bias'] = E.conv_bwd(d, x_skip, P[f'downs.{lvl}.weight'], 2, 0,
+                                                                            add_to_dx=dskips[lvl])
+            d = _seq_bwd(d, P, f'encoders.{lvl}.layers.', cfg['enc_blk_nums'][lvl], sv_e, Kt, dK, G)
+        dinp, G['intro.weight'], G['intro.bias'] = E.conv_bwd(d, inp_p, P['intro.weight'], 1, 1, need_dx=True, add_to_dx=dout)
+        if (Hp, Wp) != (H0, W0):
+            dinp = K.pad_crop(dinp, H0, W0)
+        dkv = proj_bwd(tab, kvf, dK, G, need_dkv)
+        return dinp, dkv, G, dK

@@ -2286,3 +2286,93 @@ def convt4_grad_from_3x3(dw3, db4, Cin, Cout):
     db = torch.empty(Cout, dtype=torch.float32, device=dw3.device) if db4 is not None else None
     check(_lib.load().tdr_convt4_grad_from_3x3(dw3.data_ptr(), _p(db4), Cin, Cout, dw.data_ptr(), _p(db), _stream()), 'tdr_convt4_grad_from_3x3')
     return dw, db
+
+
+# ---------------------------------------------------------------------------- NAFNetDynamicFusion (csrc/tdr_dynfusion.hip)
+def _rowvec(v):
+    """a [N, k] row slice of a wider [N, ld] tensor (a slice of the projection output): (pointer, image stride)"""
+    assert v.dim() == 2 and v.stride(1) == 1
+    return v.data_ptr(), v.stride(0)
+
+
+def kvproj_fwd(table, nseg, ntiles, kv, ld):
+    """kv [N, K] -> [N, ld]: every projection of the table (include/tdr.h, tdr_kvproj_fwd)"""
+    N, Kd = kv.shape
+    out = torch.empty(N, ld, dtype=torch.float32, device=kv.device)
+    check(_lib.load().tdr_kvproj_fwd(table.data_ptr(), nseg, ntiles, kv.data_ptr(), N, Kd, out.data_ptr(), ld, _stream()), 'tdr_kvproj_fwd')
+    return out
+
+
+def kvproj_wgrad(table, gtable, nseg, ntiles, kv, dk):
+    N, Kd = kv.shape
+    check(_lib.load().tdr_kvproj_wgrad(table.data_ptr(), gtable.data_ptr(), nseg, ntiles, kv.data_ptr(), dk.data_ptr(), dk.stride(0), N,
+                                       Kd, _stream()), 'tdr_kvproj_wgrad')
+
+
+def kvproj_dkv(table, nseg, ntiles, dk, Kd):
+    lib = _lib.load()
+    N = dk.shape[0]
+    dkv = torch.empty(N, Kd, dtype=torch.float32, device=dk.device)
+    ws = workspace(lib.tdr_kvproj_dkv_ws_floats(ntiles, N, Kd), dk.device, 'kvproj')
+    check(lib.tdr_kvproj_dkv(table.data_ptr(), nseg, ntiles, dk.data_ptr(), dk.stride(0), N, Kd, dkv.data_ptr(), ws.data_ptr(), _stream()),
+          'tdr_kvproj_dkv')
+    return dkv
+
+
+def modln_fwd(x, a, b, w, lb, eps):
+    """LayerNorm2d of x * a + b (a, b: [N, C] row slices) -> (y, mu, rstd)"""
+    N, Cc, H, W = x.shape
+    assert x.is_contiguous()
+    (pa, ns), (pb, nsb) = _rowvec(a), _rowvec(b)
+    assert ns == nsb
+    y = torch.empty_like(x)
+    mu = torch.empty(N, H * W, dtype=torch.float32, device=x.device)
+    rs = torch.empty_like(mu)
+    check(_lib.load().tdr_modln_fwd(x.data_ptr(), pa, pb, ns, w.data_ptr(), lb.data_ptr(), float(eps), N, Cc, H * W, y.data_ptr(),
+                                    mu.data_ptr(), rs.data_ptr(), _stream()), 'tdr_modln_fwd')
+    return y, mu, rs
+
+
+def nc_affine(x, a, b):
+    N, Cc, H, W = x.shape
+    assert x.is_contiguous()
+    (pa, ns), (pb, _) = _rowvec(a), _rowvec(b)
+    y = torch.empty_like(x)
+    check(_lib.load().tdr_nc_affine(x.data_ptr(), pa, pb, ns, N, Cc, H * W, y.data_ptr(), _stream()), 'tdr_nc_affine')
+    return y
+
+
+def nc_affine_bwd(dm, x, a, da, db, add=None):
+    """dx = a dm (+ add); da / db ([N, C] row slices, written) = sum_hw dm x, sum_hw dm"""
+    N, Cc, H, W = x.shape
+    assert dm.is_contiguous() and x.is_contiguous() and (add is None or add.is_contiguous())
+    pa, ns = _rowvec(a)
+    (pda, dns), (pdb, _) = _rowvec(da), _rowvec(db)
+    dx = torch.empty_like(x)
+    check(_lib.load().tdr_nc_affine_bwd(dm.data_ptr(), x.data_ptr(), pa, ns, _p(add), N, Cc, H * W, dx.data_ptr(), pda, pdb, dns,
+                                        _stream()), 'tdr_nc_affine_bwd')
+    return dx
+
+
+def modgate_fwd(t, a, b, want_pool=False):
+    """t [N, 2c, H, W]: g = (t a + b)[:c] * (t a + b)[c:] (a, b: [N, 2c] row slices); pooled [N, c] = mean g when asked for"""
+    N, C2, H, W = t.shape
+    assert t.is_contiguous()
+    c = C2 // 2
+    (pa, ns), (pb, _) = _rowvec(a), _rowvec(b)
+    g = torch.empty(N, c, H, W, dtype=torch.float32, device=t.device)
+    pooled = torch.empty(N, c, dtype=torch.float32, device=t.device) if want_pool else None
+    check(_lib.load().tdr_modgate_fwd(t.data_ptr(), pa, pb, ns, N, c, H * W, g.data_ptr(), _p(pooled), _stream()), 'tdr_modgate_fwd')
+    return g, pooled
+
+
+def modgate_bwd(dg, t, a, b, da, db, dg_bias=None, dg_bias_mul=1.0):
+    N, C2, H, W = t.shape
+    assert dg.is_contiguous() and t.is_contiguous()
+    c = C2 // 2
+    (pa, ns), (pb, _) = _rowvec(a), _rowvec(b)
+    (pda, dns), (pdb, _) = _rowvec(da), _rowvec(db)
+    dt = torch.empty_like(t)
+    check(_lib.load().tdr_modgate_bwd(dg.data_ptr(), _p(dg_bias), float(dg_bias_mul), t.data_ptr(), pa, pb, ns, N, c, H * W, dt.data_ptr(),
+                                      pda, pdb, dns, _stream()), 'tdr_modgate_bwd')
+    return dt

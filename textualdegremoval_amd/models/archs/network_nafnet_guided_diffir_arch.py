@@ -1,0 +1,163 @@
+"""NAFNetDynamicFusion on the HIP engine: the NAFNet U-Net whose blocks are modulated by the textual embedding k_v [N, 10, 1024] that
+the stage-A Mapper produces (textualdegremoval_amd/i2t.py).
+
+Drop-in mirror of the reference's models/archs/network_nafnet_guided_diffir_arch.py:237-544: same class names, constructor kwargs,
+forward signatures, parameter names, registration order (= state-dict order; `middle_blks` is reassigned after `ups` / `downs` are
+registered and keeps its slot) and default initialisation (the nn members are constructed exactly like the reference's and serve as
+parameter containers; their ATen forward is never called).  All arithmetic runs in libtdr_hip.so through
+textualdegremoval_amd.dynfusion_engine.  NAFNet, NAFBlock, SimpleGate and NAFNetLocal of that file are the existing classes of
+network_nafnet_guided_arch.py (`define_network` keeps resolving them there: that module sorts first); the file's copies of the Mapper and
+the MASA helpers are left out (textualdegremoval_amd.i2t has the Mapper).
+"""
+import torch
+import torch.nn as nn
+
+from ... import dynfusion_engine as D
+from ... import engine as E
+from .nafnet_arch_utils import LayerNorm2d, require_gpu
+from .network_nafnet_guided_arch import NAFBlock, NAFNet, NAFNetLocal, SimpleGate, _named  # noqa: F401
+
+
+class _DynNetFn(torch.autograd.Function):
+    """the whole NAFNetDynamicFusion as one autograd node (gradients w.r.t. the image and k_v included)"""
+
+    @staticmethod
+    def forward(ctx, inp, kv, names, cfg, *params):
+        require_gpu(inp, 'NAFNetDynamicFusion')
+        P = dict(zip(names, [p.detach() for p in params]))
+        out, saved = D.dyn_unet_fwd(P, cfg, inp, kv.detach())
+        ctx.names, ctx.P, ctx.cfg, ctx.saved, ctx.kv_shape = names, P, cfg, saved, kv.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dinp, dkv, G, _ = D.dyn_unet_bwd(dout, ctx.P, ctx.cfg, ctx.saved, need_dkv=ctx.needs_input_grad[1])
+        ctx.saved = None
+        return ((dinp if ctx.needs_input_grad[0] else None), (dkv.view(ctx.kv_shape) if dkv is not None else None), None, None) + \
+            tuple(G[k] for k in ctx.names)
+
+
+class _DynBlockFn(torch.autograd.Function):
+    """one NAFBlock_DynamicFusion (reference :350-375), its three projections included"""
+
+    @staticmethod
+    def forward(ctx, x, kv, names, *params):
+        require_gpu(x, 'NAFBlock_DynamicFusion')
+        P = dict(zip(names, [p.detach() for p in params]))
+        c = x.shape[1]
+        kvf = D.flat_kv(kv.detach(), x.shape[0])
+        tab, Kt = D.proj_fwd(P, [('', c)], kvf)
+        out, saved = D.dyn_naf_fwd(x.contiguous(), P, Kt, 0)
+        ctx.names, ctx.P, ctx.saved, ctx.kv_shape, ctx.proj = names, P, saved, kv.shape, (tab, kvf, Kt)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        tab, kvf, Kt = ctx.proj
+        dK = torch.empty_like(Kt)
+        with E.deferred_join():
+            dx, G = D.dyn_naf_bwd(dout.contiguous(), ctx.P, ctx.saved, Kt, dK)
+            dkv = D.proj_bwd(tab, kvf, dK, G, ctx.needs_input_grad[1])
+        ctx.saved = ctx.proj = None
+        return (dx, (dkv.view(ctx.kv_shape) if dkv is not None else None), None) + tuple(G[k] for k in ctx.names)
+
+
+class SimpleGate_DynamicFusion(nn.Module):
+    """the embedding-modulated SimpleGate (reference :250-275): fused into the modulation kernels of the block on the HIP path; kept as
+    the container of its projection `kernel` (Linear(10 * 1024, 2 dim, bias=False))"""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.kernel = nn.Sequential(nn.Linear(10 * 1024, dim * 2, bias=False))
+
+    def forward(self, x, k_v):
+        raise RuntimeError('SimpleGate_DynamicFusion is fused into the block kernels on the HIP path (call NAFBlock_DynamicFusion)')
+
+
+class NAFBlock_DynamicFusion(nn.Module):
+    def __init__(self, c, DW_Expand=2, FFN_Expand=2, drop_out_rate=0.):
+        super().__init__()
+        if DW_Expand != 2 or FFN_Expand != 2 or drop_out_rate > 0.:
+            raise NotImplementedError('HIP path: NAFBlock_DynamicFusion with DW_Expand=FFN_Expand=2, no dropout (reference defaults)')
+        self.kernel = nn.Sequential(nn.Linear(10 * 1024, c * 2, bias=False))
+        dw_channel = c * DW_Expand
+        self.conv1 = nn.Conv2d(c, dw_channel, 1, padding=0, stride=1, groups=1, bias=True)
+        self.conv2 = nn.Conv2d(dw_channel, dw_channel, 3, padding=1, stride=1, groups=dw_channel, bias=True)
+        self.conv3 = nn.Conv2d(dw_channel // 2, c, 1, padding=0, stride=1, groups=1, bias=True)
+        self.sca = nn.Sequential(nn.AdaptiveAvgPool2d(1),
+                                 nn.Conv2d(dw_channel // 2, dw_channel // 2, 1, padding=0, stride=1, groups=1, bias=True))
+        self.sg1 = SimpleGate_DynamicFusion(dim=c * 2)
+        self.sg2 = SimpleGate_DynamicFusion(dim=c * 2)
+        ffn_channel = FFN_Expand * c
+        self.conv4 = nn.Conv2d(c, ffn_channel, 1, padding=0, stride=1, groups=1, bias=True)
+        self.conv5 = nn.Conv2d(ffn_channel // 2, c, 1, padding=0, stride=1, groups=1, bias=True)
+        self.norm1 = LayerNorm2d(c)
+        self.norm2 = LayerNorm2d(c)
+        self.dropout1 = nn.Identity()
+        self.dropout2 = nn.Identity()
+        self.beta = nn.Parameter(torch.zeros((1, c, 1, 1)), requires_grad=True)
+        self.gamma = nn.Parameter(torch.zeros((1, c, 1, 1)), requires_grad=True)
+
+    def forward(self, inp, k_v):
+        names, params = _named(self)
+        return _DynBlockFn.apply(inp, k_v, names, *params)
+
+
+class DynamicBasicLayer(nn.Module):
+    def __init__(self, chan, num):
+        super().__init__()
+        self.layers = nn.ModuleList()
+        for _ in range(num):
+            self.layers.append(NAFBlock_DynamicFusion(chan))
+
+    def forward(self, x, k_v):
+        for layer in self.layers:
+            x = layer(x, k_v)
+        return x
+
+
+class NAFNetDynamicFusion(nn.Module):
+    def __init__(self, img_channel=3, width=16, middle_blk_num=1, enc_blk_nums=[], dec_blk_nums=[]):
+        super().__init__()
+        if len(enc_blk_nums) != len(dec_blk_nums):
+            raise ValueError('NAFNetDynamicFusion: one decoder level per encoder level (the skips are zipped, reference :528-531)')
+        self.intro = nn.Conv2d(img_channel, width, 3, padding=1, stride=1, groups=1, bias=True)
+        self.ending = nn.Conv2d(width, img_channel, 3, padding=1, stride=1, groups=1, bias=True)
+        self.encoders = nn.ModuleList()
+        self.decoders = nn.ModuleList()
+        self.middle_blks = nn.ModuleList()
+        self.ups = nn.ModuleList()
+        self.downs = nn.ModuleList()
+        chan = width
+        for num in enc_blk_nums:
+            self.encoders.append(DynamicBasicLayer(chan, num))
+            self.downs.append(nn.Conv2d(chan, 2 * chan, 2, 2))
+            chan = chan * 2
+        self.middle_blks = DynamicBasicLayer(chan, middle_blk_num)       # (keeps the slot registered above, as in the reference)
+        for num in dec_blk_nums:
+            self.ups.append(nn.Sequential(nn.Conv2d(chan, chan * 2, 1, bias=False), nn.PixelShuffle(2)))
+            chan = chan // 2
+            self.decoders.append(DynamicBasicLayer(chan, num))
+        self.padder_size = 2 ** len(self.encoders)
+        self.cfg = dict(img_channel=img_channel, width=width, middle_blk_num=middle_blk_num, enc_blk_nums=list(enc_blk_nums),
+                        dec_blk_nums=list(dec_blk_nums))
+
+    def check_image_size(self, x):
+        from ... import kernels as K
+        _, _, h, w = x.shape
+        m = self.padder_size
+        return K.pad_crop(x.contiguous(), -(-h // m) * m, -(-w // m) * m)
+
+    def forward(self, inp, k_v):
+        D.flat_kv(k_v, inp.shape[0])          # (shape checks first: a 20-word embedding fails as in the reference, defect R10)
+        names, params = _named(self)
+        return _DynNetFn.apply(inp, k_v, names, self.cfg, *params)
+
+
+class NAFNetLocalDynamic(NAFNetDynamicFusion):
+    """The reference's TLSC wrapper of NAFNetDynamicFusion (:547-557) cannot be constructed there: Local_Base.convert
+    (nafnet_local_arch.py:106-111) runs `self.forward(imgs)` without k_v -- defect R11.  Same error here."""
+
+    def __init__(self, *args, train_size=(1, 3, 256, 256), fast_imp=False, **kwargs):
+        raise TypeError("NAFNetDynamicFusion.forward() missing 1 required positional argument: 'k_v' "
+                        "(NAFNetLocalDynamic cannot be constructed in the reference either: defect R11)")
