@@ -1,7 +1,7 @@
 """Hand-written forward/backward of DRSformer-ref without the MEFC sub-network (`DRSformer200L_SPA_RefFusion`,
 models/archs/network_drsformer_guided_arch_200L_SPA.py of the reference) on the HIP kernels -- SURVEY.md 8f, second "next"
-architecture.  Topology = Restormer-ref minus the refinement stage (restormer_engine's MASA front-end, dense convs,
-Down/Upsample, LayerNorm are reused); the blocks differ:
+architecture, and of the full `DRSformerRefFusion` / un-guided `DRSformer` with MEFC.  The network is restormer_engine's U-Net
+walk (MASA front-end, dense convs, Down/Upsample, LayerNorm, fusion blocks) without the refinement blocks; the blocks differ:
 
 * Top-K Sparse Attention (:257-328): the four masked softmaxes all multiply the same v, so they collapse into ONE c x c
   matrix A = sum_m attn_m * softmax(topk_m(logits)) (tdr_tksa_softmax) and the MDTA data flow is unchanged: q k^T as a
@@ -20,8 +20,6 @@ import torch
 from . import engine as E
 from . import kernels as K
 from . import restormer_engine as R
-
-PADDER_LOG2 = 3
 
 
 def _am(P):
@@ -152,153 +150,32 @@ def tblock_bwd(dout, P, heads, ln_type, saved):
     return dx, G
 
 
-def fblock_fwd(x, P, heads, ln_type):
-    z, sv = tblock_fwd(x, P, heads, ln_type)
-    return K.axpby_dev(z, P['alpha'], x), (sv, z)
-
-
-def fblock_bwd(dout, P, heads, ln_type, saved):
-    sv, z = saved
-    dalpha = K.dot(dout, z)
-    dz = K.axpby_dev(dout, P['alpha'])
-    with E.deferred_join():
-        dx, G = tblock_bwd(dz, P, heads, ln_type, sv)
-    G['alpha'] = dalpha
-    dx = K.add_(dx, dout)
-    E.maybe_join()
-    return dx, G
-
-
-def seq_fwd(x, P, pre, n, heads, ln_type, fusion=False):
-    saved = []
-    for i in range(n):
-        x, sv = (fblock_fwd if fusion else tblock_fwd)(x, E._sub(P, f'{pre}{i}.'), heads, ln_type)
-        saved.append(sv)
-    return x, saved
-
-
-def seq_bwd(d, P, pre, n, heads, ln_type, saved, G, fusion=False):
-    for i in reversed(range(n)):
-        E.set_late_prefix(f'{pre}{i}.')
-        d, g = (fblock_bwd if fusion else tblock_bwd)(d, E._sub(P, f'{pre}{i}.'), heads, ln_type, saved[i])
-        E._put(G, f'{pre}{i}.', g)
-    E.set_late_prefix('')
-    return d
+# ---------------------------------------------------------------------------
+# whole network: restormer_engine's walk with these blocks, no refinement blocks; MEFC sub-networks after the patch embedding and
+# after decoder_level1 in DRSformerRefFusion / DRSformer (cfg['mefc']), none in DRSformer200L_SPA_RefFusion
+# ---------------------------------------------------------------------------
+def _stage(fn, pre):
+    """mefc_fwd / mefc_bwd on the sub-network `pre` as a stage of the walk (restormer_engine.walk_fwd / walk_bwd)"""
+    return lambda x, P, cfg, *rest: fn(x, P, pre, *rest)
 
 
 def net_fwd(P, cfg, inp, ref):
     """ref = None: the UN-GUIDED `DRSformer` of the same file (network_drsformer_guided_arch.py:586-676): no MASA pyramid, no
     fusion blocks, no padding (its PixelUnshuffle raises on sizes that are not multiples of 8), MEFC sub-networks always."""
-    N = inp.shape[0]
-    guided = ref is not None
-    if guided:
-        pyr, (H0, W0, Hp, Wp) = E.pyramids_fwd(P, cfg, inp, ref, PADDER_LOG2, 4)
-        warp, sv_masa = E.masa_fwd(pyr.lq_deep, pyr.ref_feats, N, pyr.geo)
-    else:
-        H0, W0 = inp.shape[2:]
-        if H0 % 8 or W0 % 8:
-            raise ValueError(f'DRSformer: H, W must be multiples of 8 (three PixelUnshuffle(2) stages); got {H0}x{W0}')
-        Hp, Wp = H0, W0
-        import types
-        pyr, warp, sv_masa = types.SimpleNamespace(inp_p=inp.contiguous(), geo=None), None, None
-    inp_p, geo = pyr.inp_p, pyr.geo
-    hd, ln, nb, nfz, dim = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg.get('reffusion_n_blocks'), cfg['dim']
     full = bool(cfg.get('mefc'))       # DRSformerRefFusion: MEFC sub-networks + a working level-1 fusion; else the 200L_SPA class
-    x = E.conv_fwd(inp_p, P['patch_embed.proj.weight'], P.get('patch_embed.proj.bias'), 1, 1)
-    x_embed, sv_m0 = x, None
-    if full:
-        x, sv_m0 = mefc_fwd(x, P, 'encoder_level0.')
-    sv_lv, enc_out = [], []
-    for l in range(4):
-        c = dim * 2 ** l
-        sv_f = None
-        if guided and (l > 0 or full):   # R6 (200L_SPA only): the reference discards the level-1 fusion; it is not computed there
-            f, sv_f = seq_fwd(K.concat2(x, warp[l]), P, R._FUS[l], nfz[l], hd[l], ln, fusion=True)
-            x = K.slice_channels(f, 0, c)
-        e, sv_e = seq_fwd(x, P, R._ENC[l], nb[l], hd[l], ln)
-        enc_out.append(e)
-        sv_lv.append((sv_f, sv_e))
-        if l < 3:
-            x = R.down_fwd(e, P[R._DOWN[l]])
-    e1, e2, e3, lat = enc_out
-    cat3 = K.concat2(R.up_fwd(lat, P['up4_3.body.0.weight']), e3)
-    d3, sv_d3 = seq_fwd(R._pw_fwd(cat3, P, 'reduce_chan_level3'), P, 'decoder_level3.', nb[2], hd[2], ln)
-    cat2 = K.concat2(R.up_fwd(d3, P['up3_2.body.0.weight']), e2)
-    d2, sv_d2 = seq_fwd(R._pw_fwd(cat2, P, 'reduce_chan_level2'), P, 'decoder_level2.', nb[1], hd[1], ln)
-    cat1 = K.concat2(R.up_fwd(d2, P['up2_1.body.0.weight']), e1)
-    d1, sv_d1 = seq_fwd(cat1, P, 'decoder_level1.', nb[0], hd[0], ln)
-    sv_m1 = None
-    if full:
-        d1, sv_m1 = mefc_fwd(d1, P, 'refinement.')
-    out_p = E.conv_fwd(d1, P['output.weight'], P.get('output.bias'), 1, 1, res=inp_p)
-    out = out_p if (Hp, Wp) == (H0, W0) else K.pad_crop(out_p, H0, W0)
-    saved = (N, (H0, W0, Hp, Wp), geo, pyr, sv_m0, sv_m1, sv_masa, sv_lv, enc_out, cat3, d3, sv_d3, cat2, d2, sv_d2, sv_d1, d1)
-    return out, saved
+    return R.walk_fwd(P, cfg, inp, ref, 'DRSformer: H, W must be multiples of 8 (three PixelUnshuffle(2) stages); got {}x{}', tblock_fwd,
+                      fuse=range(4) if full else range(1, 4),       # R6 (200L_SPA): the level-1 fusion is discarded; not computed here
+                      head=_stage(mefc_fwd, 'encoder_level0.') if full else None, tail=_stage(mefc_fwd, 'refinement.') if full else None)
 
 
 def net_bwd(dout, P, cfg, saved, G=None):
-    G = {} if G is None else G
-    with E.deferred_join(), E.late_leaves(G):       # (leaf 1x1 weight gradients: engine.DEFER_WGRAD)
-        return _net_bwd(dout, P, cfg, saved, G)
-
-
-def _net_bwd(dout, P, cfg, saved, G):
-    (N, (H0, W0, Hp, Wp), geo, pyr, sv_m0, sv_m1, sv_masa, sv_lv, enc_out, cat3, d3, sv_d3, cat2, d2, sv_d2, sv_d1, d1) = saved
     full = bool(cfg.get('mefc'))
-    G = {} if G is None else G
-    hd, ln, nb, nfz, dim = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg.get('reffusion_n_blocks'), cfg['dim']
-    e1, e2, e3, lat = enc_out
-    inp_p = pyr.inp_p
-    dout = dout.contiguous()
-    if (Hp, Wp) != (H0, W0):
-        dout = K.pad_crop(dout, Hp, Wp)
-    has_ob = 'output.bias' in P
-    d, G['output.weight'], db = E.conv_bwd(dout, d1, P['output.weight'], 1, 1, bias=has_ob)
-    if has_ob:
-        G['output.bias'] = db
-    if full:
-        d = mefc_bwd(d, P, 'refinement.', sv_m1, G)
-    d = seq_bwd(d, P, 'decoder_level1.', nb[0], hd[0], ln, sv_d1, G)
-    de1 = d[:, dim:]
-    d, G['up2_1.body.0.weight'] = R.up_bwd(K.slice_channels(d, 0, dim), d2, P['up2_1.body.0.weight'])
-    d = seq_bwd(d, P, 'decoder_level2.', nb[1], hd[1], ln, sv_d2, G)
-    d = R._pw_bwd(d, cat2, P, 'reduce_chan_level2', G)
-    de2 = d[:, 2 * dim:]
-    d, G['up3_2.body.0.weight'] = R.up_bwd(K.slice_channels(d, 0, 2 * dim), d3, P['up3_2.body.0.weight'])
-    d = seq_bwd(d, P, 'decoder_level3.', nb[2], hd[2], ln, sv_d3, G)
-    d = R._pw_bwd(d, cat3, P, 'reduce_chan_level3', G)
-    de3 = d[:, 4 * dim:]
-    d, G['up4_3.body.0.weight'] = R.up_bwd(K.slice_channels(d, 0, 4 * dim), lat, P['up4_3.body.0.weight'])
-    dskip = [de1, de2, de3]
-    dwarp = [None] * 4
-    for l in reversed(range(4)):
-        c = dim * 2 ** l
-        sv_f, sv_e = sv_lv[l]
-        d = seq_bwd(d, P, R._ENC[l], nb[l], hd[l], ln, sv_e, G)
-        if sv_f is not None:
-            df = torch.zeros(N, 2 * c, d.shape[2], d.shape[3], dtype=torch.float32, device=d.device)
-            K.copy_rows(d, c * d.shape[2] * d.shape[3], df, 2 * c * d.shape[2] * d.shape[3], N, c * d.shape[2] * d.shape[3])
-            dcat = seq_bwd(df, P, R._FUS[l], nfz[l], hd[l], ln, sv_f, G, fusion=True)
-            dwarp[l] = dcat[:, c:]
-            d = K.slice_channels(dcat, 0, c)
-        if l > 0:
-            d, G[R._DOWN[l - 1]] = R.down_bwd(d, enc_out[l - 1], P[R._DOWN[l - 1]])
-            d = K.add_(d, dskip[l - 1])
-        else:
-            if full:
-                d = mefc_bwd(d, P, 'encoder_level0.', sv_m0, G)
-            elif sv_masa is not None:
-                dwarp[0] = torch.zeros(N, c, d.shape[2], d.shape[3], dtype=torch.float32, device=d.device)     # R6: unused warp level
-            has_pb = 'patch_embed.proj.bias' in P
-            _, G['patch_embed.proj.weight'], db = E.conv_bwd(d, inp_p, P['patch_embed.proj.weight'], 1, 1, need_dx=False, bias=has_pb)
-            if has_pb:
-                G['patch_embed.proj.bias'] = db
-    E.run_late_leaves(G, (lambda: E.pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G)) if sv_masa is not None else (lambda: None))
-    return G
+    return R.walk_bwd(dout, P, cfg, saved, G, tblock_bwd,
+                      head=_stage(mefc_bwd, 'encoder_level0.') if full else None, tail=_stage(mefc_bwd, 'refinement.') if full else None)
 
 
 # ---------------------------------------------------------------------------
-# MEFC sub-network (`subnet`, network_drsformer_guided_arch.py:522-548) and the full DRSformerRefFusion (:679-1123)
+# MEFC sub-network (`subnet`, network_drsformer_guided_arch.py:522-548) of the full DRSformerRefFusion (:679-1123)
 # ---------------------------------------------------------------------------
 OPS = ('sep_conv_1x1', 'sep_conv_3x3', 'sep_conv_5x5', 'sep_conv_7x7', 'dil_conv_3x3', 'dil_conv_5x5', 'dil_conv_7x7', 'avg_pool_3x3')
 STEPS = 4

@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from ... import drsformer_engine as DE
 from ... import kernels as K
+from ... import restormer_engine as R
 from .nafnet_arch_utils import require_gpu
 from .network_restormer_guided_arch import Downsample, Encoder, LayerNorm, OverlapPatchEmbed, Upsample, _named  # noqa: F401
 
@@ -62,14 +63,17 @@ class _BlockFn(torch.autograd.Function):
     def forward(ctx, x, names, heads, ln_type, fusion, *params):
         require_gpu(x, 'TransformerBlock')
         P = dict(zip(names, [p.detach() for p in params]))
-        out, saved = (DE.fblock_fwd if fusion else DE.tblock_fwd)(x.contiguous(), P, heads, ln_type)
+        x = x.contiguous()
+        out, saved = R.fblock_fwd(x, P, heads, ln_type, DE.tblock_fwd) if fusion else DE.tblock_fwd(x, P, heads, ln_type)
         ctx.names, ctx.P, ctx.saved, ctx.meta = names, P, saved, (heads, ln_type, fusion)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         heads, ln_type, fusion = ctx.meta
-        dx, G = (DE.fblock_bwd if fusion else DE.tblock_bwd)(dout.contiguous(), ctx.P, heads, ln_type, ctx.saved)
+        dout = dout.contiguous()
+        dx, G = (R.fblock_bwd(dout, ctx.P, heads, ln_type, ctx.saved, DE.tblock_bwd) if fusion else
+                 DE.tblock_bwd(dout, ctx.P, heads, ln_type, ctx.saved))
         return (dx, None, None, None, None) + tuple(G[k].view_as(ctx.P[k]) for k in ctx.names)
 
 

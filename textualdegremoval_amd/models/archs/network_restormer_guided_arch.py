@@ -233,13 +233,13 @@ class _UNetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, names, cfg, *params):
         P = dict(zip(names, [p.detach() for p in params]))
-        out, saved = R.unet_fwd(P, cfg, inp)
+        out, saved = R.net_fwd(P, cfg, inp, None)
         ctx.names, ctx.P, ctx.cfg, ctx.saved = names, P, cfg, saved
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        G = R.unet_bwd(dout, ctx.P, ctx.cfg, ctx.saved)
+        G = R.net_bwd(dout, ctx.P, ctx.cfg, ctx.saved)
         ctx.saved = None
         return (None, None, None) + tuple(G[k] for k in ctx.names)
 

@@ -1,9 +1,15 @@
 """Hand-written forward/backward of Restormer-ref (models/archs/network_restormer_guided_arch.py of the
-reference) on the HIP kernels -- SURVEY.md 8a rows a13-a18.
+reference) on the HIP kernels -- SURVEY.md 8a rows a13-a18 -- and the U-Net walk of the whole Restormer family.
 
 Same conventions as engine.py (whose MASA front-end, dense-conv helpers and encoder this reuses): `*_fwd`
 returns (out, saved), `*_bwd` returns (dx, grads); parameters travel as dicts keyed by the reference's
 state-dict names.  No ATen arithmetic runs on the device: every tensor op is a call into libtdr_hip.so.
+
+walk_fwd / walk_bwd run the 4-level U-Net that RestormerRefFusion, PromptIR(-ref) and DRSformer(-ref) share, guided
+or un-guided: patch embed, encoder levels with optional MASA fusion stages and Downsample, Upsample + concat +
+reduce_chan_level* + decoder levels, output conv.  promptir_engine and drsformer_engine pass in their own blocks and
+stages (the transformer block pair, a stage before each Upsample, stages after the patch embedding and after
+decoder_level1); net_fwd / net_bwd here are Restormer's call.
 
 Reference defect R1: `RestormerRefFusion.forward` indexes the 4-level encoder pyramid one slot off (feat[4]
 of a 4-entry list, :790-793,832-846).  The only assignment under which that code runs is feat[k] = L_k;
@@ -14,6 +20,9 @@ convolution-shaped -- q k^T is a per-image weight-gradient GEMM (tdr_conv_wgrad,
 convolution with per-image weights -- and run on the MFMA kernels; csrc/tdr_mdta.hip does the c x c softmax
 algebra and emits the weights already in the packed layout those kernels read.
 """
+import contextlib
+import types
+
 import torch
 
 from . import engine as E
@@ -123,39 +132,51 @@ def tblock_bwd(dout, P, heads, ln_type, saved):
     return dx, G
 
 
-# TransformerResFusionBlock (:334-353): block(x) * alpha + x
-def fblock_fwd(x, P, heads, ln_type):
-    z, sv = tblock_fwd(x, P, heads, ln_type)
+# TransformerResFusionBlock (:334-353): block(x) * alpha + x, around the network's TransformerBlock pair (tblock_fwd / tblock_bwd
+# here, drsformer_engine's TKSA / MSFN blocks there)
+def fblock_fwd(x, P, heads, ln_type, tblock=tblock_fwd):
+    z, sv = tblock(x, P, heads, ln_type)
     return K.axpby_dev(z, P['alpha'], x), (sv, z)
 
 
-def fblock_bwd(dout, P, heads, ln_type, saved):
+def fblock_bwd(dout, P, heads, ln_type, saved, tblock=tblock_bwd):
     sv, z = saved
     dalpha = K.dot(dout, z)
     dz = K.axpby_dev(dout, P['alpha'])
     with E.deferred_join():
-        dx, G = tblock_bwd(dz, P, heads, ln_type, sv)
+        dx, G = tblock(dz, P, heads, ln_type, sv)
     G['alpha'] = dalpha
     dx = K.add_(dx, dout)
     E.maybe_join()
     return dx, G
 
 
-def seq_fwd(x, P, pre, n, heads, ln_type, fusion=False):
+def seq_fwd(x, P, pre, n, heads, ln_type, tblock=tblock_fwd, fusion=False):
     saved = []
     for i in range(n):
-        x, sv = (fblock_fwd if fusion else tblock_fwd)(x, E._sub(P, f'{pre}{i}.'), heads, ln_type)
+        Pi = E._sub(P, f'{pre}{i}.')
+        x, sv = fblock_fwd(x, Pi, heads, ln_type, tblock) if fusion else tblock(x, Pi, heads, ln_type)
         saved.append(sv)
     return x, saved
 
 
-def seq_bwd(d, P, pre, n, heads, ln_type, saved, G, fusion=False):
+def seq_bwd(d, P, pre, n, heads, ln_type, saved, G, tblock=tblock_bwd, fusion=False):
     for i in reversed(range(n)):
         E.set_late_prefix(f'{pre}{i}.')
-        d, g = (fblock_bwd if fusion else tblock_bwd)(d, E._sub(P, f'{pre}{i}.'), heads, ln_type, saved[i])
+        Pi = E._sub(P, f'{pre}{i}.')
+        d, g = fblock_bwd(d, Pi, heads, ln_type, saved[i], tblock) if fusion else tblock(d, Pi, heads, ln_type, saved[i])
         E._put(G, f'{pre}{i}.', g)
     E.set_late_prefix('')              # (top-level leaves -- reduce_chan_level*, skip_conv -- carry full names)
     return d
+
+
+def refine_fwd(x, P, cfg):
+    """the `refinement.` TransformerBlocks after decoder_level1 (Restormer, PromptIR): a `tail` stage of walk_fwd"""
+    return seq_fwd(x, P, 'refinement.', cfg['num_refinement_blocks'], cfg['heads'][0], cfg['LayerNorm_type'])
+
+
+def refine_bwd(d, P, cfg, saved, G):
+    return seq_bwd(d, P, 'refinement.', cfg['num_refinement_blocks'], cfg['heads'][0], cfg['LayerNorm_type'], saved, G)
 
 
 # ---------------------------------------------------------------------------
@@ -180,185 +201,146 @@ def up_bwd(dout, x, w):
     return dx, dw
 
 
+def _conv_bwd(dout, x, P, name, G, need_dx=True):
+    """3x3 conv `name` (patch_embed.proj, output) on E.conv_bwd's immediate path: stores dW, and db if the conv has a bias"""
+    has_b = name + '.bias' in P
+    dx, G[name + '.weight'], db = E.conv_bwd(dout, x, P[name + '.weight'], 1, 1, need_dx=need_dx, bias=has_b)
+    if has_b:
+        G[name + '.bias'] = db
+    return dx
+
+
 # ---------------------------------------------------------------------------
-# whole network  RestormerRefFusion.forward (:751-963)
+# the 4-level U-Net of the whole family (RestormerRefFusion.forward :751-963, Restormer.forward :464-501, PromptIR, DRSformer):
+# one forward walk, one backward walk; the networks differ only by the arguments their net_fwd / net_bwd pass
 # ---------------------------------------------------------------------------
 _FUS = ['masa_blk_enc_level1.', 'masa_blk_enc_level2.', 'masa_blk_enc_level3.', 'masa_blk_enc_level4.']
 _ENC = ['encoder_level1.', 'encoder_level2.', 'encoder_level3.', 'latent.']
 _DOWN = ['down1_2.body.0.weight', 'down2_3.body.0.weight', 'down3_4.body.0.weight']
+_UP = ['up2_1.body.0.weight', 'up3_2.body.0.weight', 'up4_3.body.0.weight']        # _UP[l]: into decoder level l + 1
 
 
-def net_fwd(P, cfg, inp, ref):
-    """inp, ref [N,3,H,W] -> (out [N,3,H,W], saved).  cfg: constructor kwargs of RestormerRefFusion."""
+def walk_fwd(P, cfg, inp, ref, size_msg, tblock=tblock_fwd, fuse=range(4), head=None, pre_up=None, tail=None, dual_pixel=False):
+    """inp [N,C,H,W] -> (out, saved).
+    ref [N,C,Hr,Wr]: guided -- MASA pyramids and match (engine.pyramids_fwd / masa_fwd), zero padding to the MASA block grid
+    (reference defect R1: the pyramid is [L1..L4], padder_size 8), a fusion stage (fusion blocks on cat[x, warp_l], then the
+    first half of the channels) at each level in `fuse`.  ref None: un-guided -- no reference branch and no padding: H, W must be
+    multiples of 8 (the reference's PixelUnshuffle raises otherwise), else ValueError(size_msg.format(H, W)).
+    What the caller passes in:
+      tblock               TransformerBlock forward (x, P, heads, ln_type); the fusion blocks wrap it
+      head(x, P, cfg)      stage after the patch embedding -> (x, saved)
+      pre_up(x, P, cfg, l) stage before the Upsample into decoder level l (l = 3, 2, 1) -> (x, saved)
+      tail(x, P, cfg)      stage after decoder_level1 -> (x, saved)
+      dual_pixel           output(x + skip_conv(inp_enc_level1)) without `+ inp` (Restormer's dual-pixel task, :955-959)
+    saved = (N, (H0, W0, Hp, Wp), geo, pyr, None, None, sv_masa, S) -- the prefix of engine.net_fwd's; S holds the rest by name."""
     N = inp.shape[0]
-    pyr, (H0, W0, Hp, Wp) = E.pyramids_fwd(P, cfg, inp, ref, PADDER_LOG2, 4)
-    inp_p, geo = pyr.inp_p, pyr.geo
-    warp, sv_masa = E.masa_fwd(pyr.lq_deep, pyr.ref_feats, N, geo)
-    hd, ln, nb, nfz, dim = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg['reffusion_n_blocks'], cfg['dim']
-
-    x = E.conv_fwd(inp_p, P['patch_embed.proj.weight'], P.get('patch_embed.proj.bias'), 1, 1)
-    sv_lv, enc_out = [], []
+    if ref is not None:
+        pyr, sizes = E.pyramids_fwd(P, cfg, inp, ref, PADDER_LOG2, 4)
+        warp, sv_masa = E.masa_fwd(pyr.lq_deep, pyr.ref_feats, N, pyr.geo)
+    else:
+        H, W = inp.shape[2:]
+        if H % 8 or W % 8:
+            raise ValueError(size_msg.format(H, W))
+        pyr, sizes, sv_masa, fuse = types.SimpleNamespace(inp_p=inp.contiguous(), geo=None), (H, W, H, W), None, ()
+    hd, ln, nb, nfz = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg.get('reffusion_n_blocks')
+    S = types.SimpleNamespace(head=None, levels=[], enc=[], dec=[None] * 3, tail=None)
+    x = E.conv_fwd(pyr.inp_p, P['patch_embed.proj.weight'], P.get('patch_embed.proj.bias'), 1, 1)
+    if head:
+        x, S.head = head(x, P, cfg)
     for l in range(4):
-        c = dim * 2 ** l
-        f, sv_f = seq_fwd(K.concat2(x, warp[l]), P, _FUS[l], nfz[l], hd[l], ln, fusion=True)
-        x = K.slice_channels(f, 0, c)                      # `[:, :embed_dim // 2]` (:892,903,914,925)
+        sv_f = None
+        if l in fuse:
+            f, sv_f = seq_fwd(K.concat2(x, warp[l]), P, _FUS[l], nfz[l], hd[l], ln, tblock, fusion=True)
+            x = K.slice_channels(f, 0, x.shape[1])         # `[:, :embed_dim // 2]` (:892,903,914,925)
         if l == 0:
-            x_l1 = x                                       # `inp_enc_level1`: what skip_conv reads when dual_pixel_task (:958)
-        e, sv_e = seq_fwd(x, P, _ENC[l], nb[l], hd[l], ln)
-        enc_out.append(e)
-        sv_lv.append((sv_f, sv_e))
+            S.x_l1 = x                                     # `inp_enc_level1`: what skip_conv reads when dual_pixel
+        e, sv_e = seq_fwd(x, P, _ENC[l], nb[l], hd[l], ln, tblock)
+        S.enc.append(e)
+        S.levels.append((sv_f, sv_e))
         if l < 3:
             x = down_fwd(e, P[_DOWN[l]])
-    e1, e2, e3, lat = enc_out
-    cat3 = K.concat2(up_fwd(lat, P['up4_3.body.0.weight']), e3)
-    d3, sv_d3 = seq_fwd(_pw_fwd(cat3, P, 'reduce_chan_level3'), P, 'decoder_level3.', nb[2], hd[2], ln)
-    cat2 = K.concat2(up_fwd(d3, P['up3_2.body.0.weight']), e2)
-    d2, sv_d2 = seq_fwd(_pw_fwd(cat2, P, 'reduce_chan_level2'), P, 'decoder_level2.', nb[1], hd[1], ln)
-    cat1 = K.concat2(up_fwd(d2, P['up2_1.body.0.weight']), e1)
-    d1, sv_d1 = seq_fwd(cat1, P, 'decoder_level1.', nb[0], hd[0], ln)
-    rf, sv_rf = seq_fwd(d1, P, 'refinement.', cfg['num_refinement_blocks'], hd[0], ln)
-    if cfg.get('dual_pixel_task'):
-        # dual-pixel defocus deblurring (:955-959): output(refined + skip_conv(inp_enc_level1)), no `+ inp_img`
-        rf = _pw_fwd(x_l1, P, 'skip_conv', res=rf)
-        out_p = E.conv_fwd(rf, P['output.weight'], P.get('output.bias'), 1, 1)
-    else:
-        out_p = E.conv_fwd(rf, P['output.weight'], P.get('output.bias'), 1, 1, res=inp_p)
+    x = e                                                  # the latent
+    for l in (2, 1, 0):                                    # decoder level l + 1 on cat[Upsample(x), encoder level l + 1]
+        sv_p = None
+        if pre_up:
+            x, sv_p = pre_up(x, P, cfg, l + 1)
+        cat = K.concat2(up_fwd(x, P[_UP[l]]), S.enc[l])
+        y, sv_d = seq_fwd(_pw_fwd(cat, P, f'reduce_chan_level{l + 1}') if l else cat, P, f'decoder_level{l + 1}.', nb[l], hd[l], ln,
+                          tblock)
+        S.dec[l] = (sv_p, x, cat, sv_d)
+        x = y
+    if tail:
+        x, S.tail = tail(x, P, cfg)
+    if dual_pixel:
+        x = _pw_fwd(S.x_l1, P, 'skip_conv', res=x)
+    S.y = x
+    out_p = E.conv_fwd(x, P['output.weight'], P.get('output.bias'), 1, 1, res=None if dual_pixel else pyr.inp_p)
+    H0, W0, Hp, Wp = sizes
     out = out_p if (Hp, Wp) == (H0, W0) else K.pad_crop(out_p, H0, W0)
-    saved = (N, (H0, W0, Hp, Wp), geo, pyr, x_l1, None, sv_masa, sv_lv, enc_out, cat3, d3, sv_d3, cat2, d2, sv_d2,
-             sv_d1, rf, sv_rf)
-    return out, saved
+    return out, (N, sizes, pyr.geo, pyr, None, None, sv_masa, S)
 
 
-def net_bwd(dout, P, cfg, saved, G=None):
+def walk_bwd(dout, P, cfg, saved, G=None, tblock=tblock_bwd, head=None, pre_up=None, tail=None, dual_pixel=False, late=True):
+    """-> G, the parameter gradients of walk_fwd (the input image is data).  The stages are the backward of the ones passed to
+    walk_fwd: head(d, P, cfg, saved, G), pre_up(d, P, cfg, l, saved, G), tail(d, P, cfg, saved, G) -> gradient of the stage input.
+    late: leaf weight gradients queued (E.late_leaves) and run next to the MASA backward at the end (E.run_late_leaves)."""
     G = {} if G is None else G
-    with E.deferred_join(), E.late_leaves(G):
-        return _net_bwd(dout, P, cfg, saved, G)
-
-
-def _net_bwd(dout, P, cfg, saved, G):
-    (N, (H0, W0, Hp, Wp), geo, pyr, x_l1, _, sv_masa, sv_lv, enc_out, cat3, d3, sv_d3, cat2, d2, sv_d2, sv_d1, rf,
-     sv_rf) = saved
-    hd, ln, nb, nfz, dim = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg['reffusion_n_blocks'], cfg['dim']
-    e1, e2, e3, lat = enc_out
-    inp_p = pyr.inp_p
-    dout = dout.contiguous()
-    if (Hp, Wp) != (H0, W0):
-        dout = K.pad_crop(dout, Hp, Wp)
-    has_ob = 'output.bias' in P
-    d, G['output.weight'], db = E.conv_bwd(dout, rf, P['output.weight'], 1, 1, bias=has_ob)
-    if has_ob:
-        G['output.bias'] = db
-    dskip_l1 = _pw_bwd(d, x_l1, P, 'skip_conv', G) if cfg.get('dual_pixel_task') else None
-    d = seq_bwd(d, P, 'refinement.', cfg['num_refinement_blocks'], hd[0], ln, sv_rf, G)
-    d = seq_bwd(d, P, 'decoder_level1.', nb[0], hd[0], ln, sv_d1, G)            # grad of cat[up(d2), e1]
-    de1 = d[:, dim:]
-    d, G['up2_1.body.0.weight'] = up_bwd(K.slice_channels(d, 0, dim), d2, P['up2_1.body.0.weight'])
-    d = seq_bwd(d, P, 'decoder_level2.', nb[1], hd[1], ln, sv_d2, G)
-    d = _pw_bwd(d, cat2, P, 'reduce_chan_level2', G)
-    de2 = d[:, 2 * dim:]
-    d, G['up3_2.body.0.weight'] = up_bwd(K.slice_channels(d, 0, 2 * dim), d3, P['up3_2.body.0.weight'])
-    d = seq_bwd(d, P, 'decoder_level3.', nb[2], hd[2], ln, sv_d3, G)
-    d = _pw_bwd(d, cat3, P, 'reduce_chan_level3', G)
-    de3 = d[:, 4 * dim:]
-    d, G['up4_3.body.0.weight'] = up_bwd(K.slice_channels(d, 0, 4 * dim), lat, P['up4_3.body.0.weight'])
-    dskip = [de1, de2, de3]
-    dwarp = [None] * 4
-    for l in reversed(range(4)):
-        c = dim * 2 ** l
-        sv_f, sv_e = sv_lv[l]
-        d = seq_bwd(d, P, _ENC[l], nb[l], hd[l], ln, sv_e, G)
-        if l == 0 and dskip_l1 is not None:
-            d = K.add_(d, dskip_l1)
-        df = torch.zeros(N, 2 * c, d.shape[2], d.shape[3], dtype=torch.float32, device=d.device)
-        K.copy_rows(d, c * d.shape[2] * d.shape[3], df, 2 * c * d.shape[2] * d.shape[3], N, c * d.shape[2] * d.shape[3])
-        dcat = seq_bwd(df, P, _FUS[l], nfz[l], hd[l], ln, sv_f, G, fusion=True)
-        dwarp[l] = dcat[:, c:]
-        dx = K.slice_channels(dcat, 0, c)
-        if l > 0:
-            d, G[_DOWN[l - 1]] = down_bwd(dx, enc_out[l - 1], P[_DOWN[l - 1]])
-            d = K.add_(d, dskip[l - 1])
-        else:
-            has_pb = 'patch_embed.proj.bias' in P
-            _, G['patch_embed.proj.weight'], db = E.conv_bwd(dx, inp_p, P['patch_embed.proj.weight'], 1, 1, need_dx=False,
-                                                             bias=has_pb)
-            if has_pb:
-                G['patch_embed.proj.bias'] = db
-    E.run_late_leaves(G, lambda: E.pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G))
+    with E.deferred_join(), (E.late_leaves(G) if late else contextlib.nullcontext()):
+        N, (H0, W0, Hp, Wp), _, pyr, _, _, sv_masa, S = saved
+        hd, ln, nb, nfz = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg.get('reffusion_n_blocks')
+        dout = dout.contiguous()
+        if (Hp, Wp) != (H0, W0):
+            dout = K.pad_crop(dout, Hp, Wp)
+        d = _conv_bwd(dout, S.y, P, 'output', G)
+        dskip_l1 = _pw_bwd(d, S.x_l1, P, 'skip_conv', G) if dual_pixel else None
+        if tail:
+            d = tail(d, P, cfg, S.tail, G)
+        dskip = []
+        for l in range(3):
+            sv_p, xu, cat, sv_d = S.dec[l]
+            d = seq_bwd(d, P, f'decoder_level{l + 1}.', nb[l], hd[l], ln, sv_d, G, tblock)
+            if l:
+                d = _pw_bwd(d, cat, P, f'reduce_chan_level{l + 1}', G)
+            cu = d.shape[1] - S.enc[l].shape[1]            # d = grad of cat[Upsample(xu), encoder output]
+            dskip.append(d[:, cu:])
+            d, G[_UP[l]] = up_bwd(K.slice_channels(d, 0, cu), xu, P[_UP[l]])
+            if pre_up:
+                d = pre_up(d, P, cfg, l + 1, sv_p, G)
+        dwarp = [None] * 4
+        for l in reversed(range(4)):
+            sv_f, sv_e = S.levels[l]
+            d = seq_bwd(d, P, _ENC[l], nb[l], hd[l], ln, sv_e, G, tblock)
+            if l == 0 and dskip_l1 is not None:
+                d = K.add_(d, dskip_l1)
+            c, H, W = d.shape[1:]
+            if sv_f is not None:
+                df = torch.zeros(N, 2 * c, H, W, dtype=torch.float32, device=d.device)
+                K.copy_rows(d, c * H * W, df, 2 * c * H * W, N, c * H * W)
+                dcat = seq_bwd(df, P, _FUS[l], nfz[l], hd[l], ln, sv_f, G, tblock, fusion=True)
+                dwarp[l] = dcat[:, c:]
+                d = K.slice_channels(dcat, 0, c)
+            elif sv_masa is not None:                      # a guided level without fusion (DRSformer's R6): its warp gets no gradient
+                dwarp[l] = torch.zeros(N, c, H, W, dtype=torch.float32, device=d.device)
+            if l > 0:
+                d, G[_DOWN[l - 1]] = down_bwd(d, S.enc[l - 1], P[_DOWN[l - 1]])
+                d = K.add_(d, dskip[l - 1])
+        if head:
+            d = head(d, P, cfg, S.head, G)
+        _conv_bwd(d, pyr.inp_p, P, 'patch_embed.proj', G, need_dx=False)
+        if late:
+            E.run_late_leaves(G, lambda: E.pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G) if sv_masa is not None else None)
     return G
 
 
 # ---------------------------------------------------------------------------
-# un-guided Restormer.forward (:464-501): the same blocks without the reference branch
+# whole network: RestormerRefFusion (ref given) and the un-guided Restormer (ref None)
 # ---------------------------------------------------------------------------
-def unet_fwd(P, cfg, inp):
-    """inp [N, inp_channels, H, W], H and W multiples of 8 (the reference has no padding here: its PixelUnshuffle raises
-    otherwise) -> (out, saved)"""
-    N, _, H, W = inp.shape
-    if H % 8 or W % 8:
-        raise ValueError(f'Restormer: H, W must be multiples of 8 (three PixelUnshuffle(2) stages, :370-378); got {H}x{W}')
-    hd, ln, nb, dim = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg['dim']
-    inp = inp.contiguous()
-    x0 = E.conv_fwd(inp, P['patch_embed.proj.weight'], P.get('patch_embed.proj.bias'), 1, 1)
-    x, sv_lv, enc_out = x0, [], []
-    for l in range(4):
-        e, sv_e = seq_fwd(x, P, _ENC[l], nb[l], hd[l], ln)
-        enc_out.append(e)
-        sv_lv.append(sv_e)
-        if l < 3:
-            x = down_fwd(e, P[_DOWN[l]])
-    e1, e2, e3, lat = enc_out
-    cat3 = K.concat2(up_fwd(lat, P['up4_3.body.0.weight']), e3)
-    d3, sv_d3 = seq_fwd(_pw_fwd(cat3, P, 'reduce_chan_level3'), P, 'decoder_level3.', nb[2], hd[2], ln)
-    cat2 = K.concat2(up_fwd(d3, P['up3_2.body.0.weight']), e2)
-    d2, sv_d2 = seq_fwd(_pw_fwd(cat2, P, 'reduce_chan_level2'), P, 'decoder_level2.', nb[1], hd[1], ln)
-    cat1 = K.concat2(up_fwd(d2, P['up2_1.body.0.weight']), e1)
-    d1, sv_d1 = seq_fwd(cat1, P, 'decoder_level1.', nb[0], hd[0], ln)
-    rf, sv_rf = seq_fwd(d1, P, 'refinement.', cfg['num_refinement_blocks'], hd[0], ln)
-    if cfg.get('dual_pixel_task'):
-        rf = _pw_fwd(x0, P, 'skip_conv', res=rf)
-        out = E.conv_fwd(rf, P['output.weight'], P.get('output.bias'), 1, 1)
-    else:
-        out = E.conv_fwd(rf, P['output.weight'], P.get('output.bias'), 1, 1, res=inp)
-    return out, (inp, x0, sv_lv, enc_out, cat3, d3, sv_d3, cat2, d2, sv_d2, sv_d1, rf, sv_rf)
+def net_fwd(P, cfg, inp, ref):
+    """inp, ref [N,3,H,W] -> (out [N,3,H,W], saved).  cfg: constructor kwargs of RestormerRefFusion / Restormer."""
+    return walk_fwd(P, cfg, inp, ref, 'Restormer: H, W must be multiples of 8 (three PixelUnshuffle(2) stages, :370-378); got {}x{}',
+                    tail=refine_fwd, dual_pixel=cfg.get('dual_pixel_task'))
 
 
-def unet_bwd(dout, P, cfg, saved, G=None):
-    """-> G (parameter gradients; the input image is data)"""
-    with E.deferred_join():
-        inp, x0, sv_lv, enc_out, cat3, d3, sv_d3, cat2, d2, sv_d2, sv_d1, rf, sv_rf = saved
-        G = {} if G is None else G
-        hd, ln, nb, dim = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg['dim']
-        e1, e2, e3, lat = enc_out
-        dout = dout.contiguous()
-        has_ob = 'output.bias' in P
-        d, G['output.weight'], db = E.conv_bwd(dout, rf, P['output.weight'], 1, 1, bias=has_ob)
-        if has_ob:
-            G['output.bias'] = db
-        dskip0 = _pw_bwd(d, x0, P, 'skip_conv', G) if cfg.get('dual_pixel_task') else None
-        d = seq_bwd(d, P, 'refinement.', cfg['num_refinement_blocks'], hd[0], ln, sv_rf, G)
-        d = seq_bwd(d, P, 'decoder_level1.', nb[0], hd[0], ln, sv_d1, G)
-        de1 = d[:, dim:]
-        d, G['up2_1.body.0.weight'] = up_bwd(K.slice_channels(d, 0, dim), d2, P['up2_1.body.0.weight'])
-        d = seq_bwd(d, P, 'decoder_level2.', nb[1], hd[1], ln, sv_d2, G)
-        d = _pw_bwd(d, cat2, P, 'reduce_chan_level2', G)
-        de2 = d[:, 2 * dim:]
-        d, G['up3_2.body.0.weight'] = up_bwd(K.slice_channels(d, 0, 2 * dim), d3, P['up3_2.body.0.weight'])
-        d = seq_bwd(d, P, 'decoder_level3.', nb[2], hd[2], ln, sv_d3, G)
-        d = _pw_bwd(d, cat3, P, 'reduce_chan_level3', G)
-        de3 = d[:, 4 * dim:]
-        d, G['up4_3.body.0.weight'] = up_bwd(K.slice_channels(d, 0, 4 * dim), lat, P['up4_3.body.0.weight'])
-        dskip = [de1, de2, de3]
-        for l in reversed(range(4)):
-            d = seq_bwd(d, P, _ENC[l], nb[l], hd[l], ln, sv_lv[l], G)
-            if l > 0:
-                d, G[_DOWN[l - 1]] = down_bwd(d, enc_out[l - 1], P[_DOWN[l - 1]])
-                d = K.add_(d, dskip[l - 1])
-            else:
-                if dskip0 is not None:
-                    d = K.add_(d, dskip0)
-                has_pb = 'patch_embed.proj.bias' in P
-                _, G['patch_embed.proj.weight'], db = E.conv_bwd(d, inp, P['patch_embed.proj.weight'], 1, 1,
-                                                                 need_dx=False, bias=has_pb)
-                if has_pb:
-                    G['patch_embed.proj.bias'] = db
-        return G
+def net_bwd(dout, P, cfg, saved, G=None):
+    # the un-guided Restormer runs its leaves at once: grouped 1x1 weight gradients are not bit-identical to ungrouped ones
+    return walk_bwd(dout, P, cfg, saved, G, tail=refine_bwd, dual_pixel=cfg.get('dual_pixel_task'), late=saved[6] is not None)
