@@ -22,9 +22,9 @@ extern "C" {
 
 /* C-ABI version: bumped with every incompatible change of this header (100 rounds 1-2, 101 round 3, 102 round 4, 103 - 104
  * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
- * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*); the
+ * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*); the
  * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
-#define TDR_ABI_VERSION 108
+#define TDR_ABI_VERSION 109
 int tdr_version(void);
 const char* tdr_last_error(void);
 
@@ -375,6 +375,24 @@ int tdr_ssim3d(const float* img1, const float* img2, int H, int W, int C, float 
  * doubles; out: 1 double = mean of the SSIM map.  Filtering, the SSIM map and its mean are evaluated in double. */
 int64_t tdr_ssim_y64_ws_doubles(int H, int W);
 int tdr_ssim_y64(const float* img1, const float* img2, int H, int W, double* ws, double* out, void* stream);
+
+/* The block features of the no-reference NIQE metric -- metrics/niqe.py:10-139 (estimate_aggd_param, compute_feature and the two-scale
+ * loop of niqe; the 36 x 36 Gaussian-model tail of :140-155 is the caller's, on the host).  y [H][W] float32: the gray / Y image in
+ * [0, 255], H and W whole multiples (>= 1) of the even, square `block`.  window: 49 doubles, the 7 x 7 smoothing window of the pristine
+ * parameter file, applied as scipy.ndimage.convolve(mode='nearest') does (taps accumulated in double, the result rounded to float32);
+ * the normalised map (img - mu) / (sigma + 1) is float32 arithmetic as in the reference, the half-size image of the second scale is
+ * the float32 2 x 2 mean cv2.resize(INTER_LINEAR) gives for an exact half.  tables: [4][table_len] doubles, row 0 the alpha grid gam
+ * (np.arange(0.2, 10.001, 0.001)), row 1 r_gam = gamma(2/gam)^2 / (gamma(1/gam) gamma(3/gam)), row 2 sqrt(gamma(1/gam) / gamma(3/gam)),
+ * row 3 gamma(2/gam) / gamma(1/gam) -- computed once by the caller.  ws: tdr_niqe_ws_floats(H, W) floats; on return it holds the
+ * normalised map of scale 1 [H][W], the half-size image [H/2][W/2] and the normalised map of scale 2 [H/2][W/2], in that order.
+ * feats_out: [(H / block) * (W / block)][36] doubles, rows in the reference's order (block columns outside, block rows inside),
+ * columns 0 - 17 scale 1 and 18 - 35 scale 2, each [alpha, (beta_l + beta_r) / 2] followed by [alpha, Eq. 8 mean, beta_l, beta_r] for
+ * the shifts [0,1], [1,0], [1,1], [1,-1].  Every moment is a float64 sum in a fixed order (no atomics): repeated calls are
+ * bit-identical.  A block whose map has no negative or no positive entry gets the reference's values: alpha = gam[0] (np.argmin of
+ * all-NaN distances), NaN betas and means. */
+int64_t tdr_niqe_ws_floats(int H, int W);
+int tdr_niqe_features(const float* y, int H, int W, int block, const double* window, const double* tables, int table_len,
+                      float* ws, double* feats_out, void* stream);
 /* TLSC local average pooling -- `AvgPool2d.forward` of models/archs/nafnet_local_arch.py:10-75 (fast_imp = False, auto_pad):
  * out[p][y][x] = mean of the k1' x k2' box (k' = min(size, k)) whose top-left corner is (clamp(y - (H - hv) / 2, 0, hv - 1),
  * clamp(x - (W - wv) / 2, 0, wv - 1)), hv = H - k1' + 1, wv = W - k2' + 1: the valid box means replicate-padded back to H x W.

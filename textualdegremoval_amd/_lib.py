@@ -15,7 +15,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TDR_LIB_PATH', os.path.join(_HERE, 'libtdr_hip.so'))   # override: profiling probe builds
 
-ABI_VERSION = 108      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
+ABI_VERSION = 109      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
 c_fp = C.c_void_p      # device pointers travel as integers
 i32, i64, f32 = C.c_int, C.c_int64, C.c_float
 
@@ -343,6 +343,8 @@ SIGNATURES = {
     'tdr_nc_affine_bwd': (i32, [c_fp, c_fp, c_fp, i64, c_fp, i32, i32, i32, c_fp, c_fp, c_fp, i64, c_fp]),
     'tdr_modgate_fwd': (i32, [c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp, c_fp]),
     'tdr_modgate_bwd': (i32, [c_fp, c_fp, f32, c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp, c_fp, i64, c_fp]),
+    'tdr_niqe_ws_floats': (i64, [i32, i32]),
+    'tdr_niqe_features': (i32, [c_fp, i32, i32, i32, c_fp, c_fp, i32, c_fp, c_fp, c_fp]),
 }
 
 _lib = None

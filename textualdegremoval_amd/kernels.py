@@ -1894,6 +1894,58 @@ def ssim_y64(img1, img2):
     return float(out.item())
 
 
+_niqe_host_tables = None
+_niqe_tables = {}
+
+
+def niqe_gamma_tables():
+    """float64 [4, 9801] on the host: the alpha grid of estimate_aggd_param (metrics/niqe.py:21-24, np.arange(0.2, 10.001, 0.001)),
+    r_gam = gamma(2/a)^2 / (gamma(1/a) gamma(3/a)), and the two gamma ratios the fit needs once alpha is known:
+    sqrt(gamma(1/a) / gamma(3/a)) (:35-36) and gamma(2/a) / gamma(1/a) (Eq. 8, :62).  Computed once."""
+    global _niqe_host_tables
+    if _niqe_host_tables is None:
+        import math
+
+        import numpy as np
+        gam = np.arange(0.2, 10.001, 0.001)
+        tab = np.empty((4, gam.size), dtype=np.float64)
+        tab[0] = gam
+        for i, a in enumerate(gam):
+            r = float(np.reciprocal(a))
+            g1, g2, g3 = math.gamma(r), math.gamma(r * 2), math.gamma(r * 3)
+            tab[1, i] = g2 * g2 / (g1 * g3)
+            tab[2, i] = math.sqrt(math.gamma(1 / a) / math.gamma(3 / a))
+            tab[3, i] = math.gamma(2 / a) / math.gamma(1 / a)
+        _niqe_host_tables = tab
+    return _niqe_host_tables
+
+
+def niqe_features(y, window, block=96, return_maps=False):
+    """y [H, W] float32 device tensor (gray / Y image in [0, 255], H and W whole multiples of the even `block`), window: the 7 x 7
+    smoothing window (array-like, taken as float64) -> float64 [nblocks, 36] device tensor: the two-scale AGGD features of
+    metrics/niqe.py:109-140, rows in the reference's block order.  return_maps: also the float32 normalised maps of both scales."""
+    import numpy as np
+    assert y.dim() == 2 and y.dtype == torch.float32 and y.is_cuda and y.is_contiguous()
+    H, W = y.shape
+    lib = _lib.load()
+    dev = y.device
+    tab = _niqe_tables.get(dev.index)
+    if tab is None:
+        tab = _niqe_tables[dev.index] = torch.from_numpy(niqe_gamma_tables()).to(dev)
+    w = np.ascontiguousarray(np.asarray(window, dtype=np.float64))
+    assert w.shape == (7, 7), f'niqe_features: the window is 7 x 7, got {w.shape}'
+    wd = torch.from_numpy(w).to(dev)
+    nblocks = (H // block) * (W // block) if block > 0 else 0
+    feats = torch.empty(max(nblocks, 1), 36, dtype=torch.float64, device=dev)
+    ws = workspace(lib.tdr_niqe_ws_floats(H, W), dev, 'niqe')
+    check(lib.tdr_niqe_features(y.data_ptr(), H, W, int(block), wd.data_ptr(), tab.data_ptr(), tab.shape[1], ws.data_ptr(),
+                                feats.data_ptr(), _stream()), 'tdr_niqe_features')
+    if return_maps:
+        n1, n2 = H * W, (H // 2) * (W // 2)
+        return feats, ws[:n1].view(H, W).clone(), ws[n1 + n2:n1 + 2 * n2].view(H // 2, W // 2).clone()
+    return feats
+
+
 def local_avgpool(x, k1, k2):
     """TLSC box mean of x [N, C, H, W] with replicate padding back to H x W (nafnet_local_arch.py:10-75)"""
     lib = _lib.load()

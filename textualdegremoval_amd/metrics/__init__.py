@@ -95,3 +95,6 @@ def calculate_ssim(img1, img2, crop_border, input_order='HWC', test_y_channel=Fa
     ta = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
     tb = torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(dev)
     return float(K.ssim3d(ta, tb, max_value).item())
+
+
+from .niqe import calculate_niqe, niqe, niqe_from_features, reorder_image  # noqa: E402  (niqe.py uses to_y_channel from above)
