@@ -1,6 +1,7 @@
 """NAFNetDynamicFusion forward/backward on the HIP kernels (models/archs/network_nafnet_guided_diffir_arch.py:250-375, :445-544).
 
-The U-Net of engine.unet_fwd / unet_bwd with every block conditioned on the textual embedding k_v [N, 10, 1024]: per block of width c
+The U-Net is engine.walk_fwd / walk_bwd, called with this module's block sequence (_seq_fwd / _seq_bwd); what lives here is the block,
+the projections and their table.  Every block is conditioned on the textual embedding k_v [N, 10, 1024]: per block of width c
 the projections `kernel` (2c outputs), `sg1.kernel` (4c) and `sg2.kernel` (4c) of the flattened k_v give per-(image, channel) affines
 
     m = x a0 + b0 -> norm1 -> conv1 -> dw3x3 -> u = dw a1 + b1 ; g = u[:c] u[c:] -> SCA -> conv3 ; y = x + (.) beta
@@ -197,58 +198,20 @@ def flat_kv(kv, N):
 
 
 def dyn_unet_fwd(P, cfg, inp, kv):
-    """NAFNetDynamicFusion.forward (:512-536) -> (out, saved)"""
-    n_enc = len(cfg['enc_blk_nums'])
-    N, _, H0, W0 = inp.shape
-    kvf = flat_kv(kv, N)
+    """NAFNetDynamicFusion.forward (:512-536) -> (out, saved): engine.walk_fwd over the modulated blocks; saved = the walk's
+    + (kvf, Kt, projection table)"""
+    kvf = flat_kv(kv, inp.shape[0])
     tab, Kt = proj_fwd(P, block_prefixes(cfg), kvf)
-    mult = 1 << n_enc
-    Hp, Wp = -(-H0 // mult) * mult, -(-W0 // mult) * mult
-    inp_p = inp.contiguous() if (Hp, Wp) == (H0, W0) else K.pad_crop(inp.contiguous(), Hp, Wp)
-    x = E.conv_fwd(inp_p, P['intro.weight'], P['intro.bias'], 1, 1)
-    sv_levels, skips = [], []
-    for lvl in range(n_enc):
-        x, sv_e = _seq_fwd(x, P, f'encoders.{lvl}.layers.', cfg['enc_blk_nums'][lvl], Kt, tab)
-        skips.append(x)
-        sv_levels.append((sv_e, x))
-        x = E.conv_fwd(x, P[f'downs.{lvl}.weight'], P[f'downs.{lvl}.bias'], 2, 0)
-    x, sv_m = _seq_fwd(x, P, 'middle_blks.layers.', cfg['middle_blk_num'], Kt, tab)
-    sv_dec = []
-    for lvl in range(len(cfg['dec_blk_nums'])):
-        xin = x
-        x = E.up_fwd(xin, P[f'ups.{lvl}.0.weight'], skips[-1 - lvl])
-        x, sv_d = _seq_fwd(x, P, f'decoders.{lvl}.layers.', cfg['dec_blk_nums'][lvl], Kt, tab)
-        sv_dec.append((xin, sv_d))
-    out_p = E.conv_fwd(x, P['ending.weight'], P['ending.bias'], 1, 1, res=inp_p)
-    out = out_p if (Hp, Wp) == (H0, W0) else K.pad_crop(out_p, H0, W0)
-    return out, ((H0, W0, Hp, Wp), inp_p, sv_levels, sv_m, sv_dec, x, kvf, Kt, tab)
+    out, saved = E.walk_fwd(P, cfg, inp, seq=lambda x, P, pre, n: _seq_fwd(x, P, pre + 'layers.', n, Kt, tab))
+    return out, saved + (kvf, Kt, tab)
 
 
 def dyn_unet_bwd(dout, P, cfg, saved, need_dkv=True, G=None):
     """-> (dinp, dkv or None, G, dK): gradients w.r.t. the image, k_v (shape [N, 10240]), every parameter, and the projection outputs"""
-    with E.deferred_join():
-        (H0, W0, Hp, Wp), inp_p, sv_levels, sv_m, sv_dec, xe, kvf, Kt, tab = saved
-        n_enc = len(cfg['enc_blk_nums'])
-        G = {} if G is None else G
-        dK = torch.empty_like(Kt)            # every column is written by exactly one block's reductions
-        dout = dout.contiguous()
-        if (Hp, Wp) != (H0, W0):
-            dout = K.pad_crop(dout, Hp, Wp)
-        d, G['ending.weight'], G['ending.bias'] = E.conv_bwd(dout, xe, P['ending.weight'], 1, 1)
-        dskips = [None] * n_enc
-        for lvl in reversed(range(len(cfg['dec_blk_nums']))):
-            xin, sv_d = sv_dec[lvl]
-            d = _seq_bwd(d, P, f'decoders.{lvl}.layers.', cfg['dec_blk_nums'][lvl], sv_d, Kt, dK, G)
-            dskips[n_enc - 1 - lvl] = d
-            d, G[f'ups.{lvl}.0.weight'] = E.up_bwd(d, xin, P[f'ups.{lvl}.0.weight'])
-        d = _seq_bwd(d, P, 'middle_blks.layers.', cfg['middle_blk_num'], sv_m, Kt, dK, G)
-        for lvl in reversed(range(n_enc)):
-            sv_e, x_skip = sv_levels[lvl]
-            d, G[f'downs.{lvl}.weight'], G[f'downs.{lvl}.bias'] = E.conv_bwd(d, x_skip, P[f'downs.{lvl}.weight'], 2, 0,
-                                                                            add_to_dx=dskips[lvl])
-            d = _seq_bwd(d, P, f'encoders.{lvl}.layers.', cfg['enc_blk_nums'][lvl], sv_e, Kt, dK, G)
-        dinp, G['intro.weight'], G['intro.bias'] = E.conv_bwd(d, inp_p, P['intro.weight'], 1, 1, need_dx=True, add_to_dx=dout)
-        if (Hp, Wp) != (H0, W0):
-            dinp = K.pad_crop(dinp, H0, W0)
+    kvf, Kt, tab = saved[-3:]
+    dK = torch.empty_like(Kt)            # every column is written by exactly one block's reductions
+    with E.deferred_join():              # (the walk's side branch is joined after the projection launches)
+        dinp, G = E.walk_bwd(dout, P, cfg, saved, G,
+                             seq=lambda d, P, pre, n, sv, G: _seq_bwd(d, P, pre + 'layers.', n, sv, Kt, dK, G))
         dkv = proj_bwd(tab, kvf, dK, G, need_dkv)
-        return dinp, dkv, G, dK
+    return dinp, dkv, G, dK

@@ -5,8 +5,14 @@ mirror the reference modules they replace and cite them; parameters are passed
 as dicts keyed by the reference's state-dict names, gradients come back keyed
 the same way.  No ATen arithmetic runs on the device here: every tensor op is a
 call into libtdr_hip.so (torch only allocates and views memory).
+
+The U-Net itself is walked by ONE pair, walk_fwd / walk_bwd: NAFNetRefFusion (net_fwd / net_bwd: a reference image, MASA
+pyramids and fusion blocks), NAFNet / NAFNetLocal (unet_fwd / unet_bwd) and NAFNetDynamicFusion (dynfusion_engine, its own
+block sequence) are callers that differ by arguments.
 """
+import contextlib
 import os
+import types
 
 import torch
 
@@ -795,50 +801,18 @@ def masa_bwd(dwarp, lq4, ref_feats, N, geo, saved, dlq_out, dref_out):
     K.copy_rows(dlq4, Cc * H * W, dlq_out, Cc * H * W, N, Cc * H * W)
 
 
-# ---------------------------------------------------------------------------
-# whole network  NAFNetRefFusion.forward (:587-740)
-# ---------------------------------------------------------------------------
-def net_fwd(P, cfg, inp, ref):
-    """inp, ref [N,3,H,W] -> (out [N,3,H,W], saved).  cfg: constructor kwargs."""
-    n_enc = len(cfg['enc_blk_nums'])
-    N = inp.shape[0]
-    pyr, (H0, W0, Hp, Wp) = pyramids_fwd(P, cfg, inp, ref, n_enc, n_enc + 1)
-    inp_p, geo = pyr.inp_p, pyr.geo
-    # cat([x, warp], 1) of every fusion level (:719,727) without copies: the transfer kernel writes the warped reference
-    # features into the second half of the level's concat buffer, the conv that produces x writes the first half
-    chan = P['intro.weight'].shape[0]
-    cats = []
-    for lvl in range(n_enc + 1):
-        Cl = pyr.ref_feats[lvl].shape[1]             # warped-feature channels (nf * 2^lvl) next to the chan * 2^lvl of x
-        cats.append(torch.empty(N, (chan << lvl) + Cl, Hp >> lvl, Wp >> lvl, dtype=torch.float32, device=inp.device))
-    warp, sv_masa = masa_fwd(pyr.lq_deep, pyr.ref_feats, N, geo, outs=[c[:, chan << lvl:] for lvl, c in enumerate(cats)])
-
-    conv_fwd(inp_p, P['intro.weight'], P['intro.bias'], 1, 1, out=cats[0][:, :chan])
-    sv_levels, skips = [], []
-    for lvl in range(n_enc):
-        x, sv_f = naf_seq_fwd(cats[lvl], P, f'masa_blk_enc.{lvl}.', cfg['reffusion_n_blocks'][lvl], c_out_last=chan)
-        x, sv_e = naf_seq_fwd(x, P, f'encoders.{lvl}.', cfg['enc_blk_nums'][lvl])
-        skips.append(x)
-        conv_fwd(x, P[f'downs.{lvl}.weight'], P[f'downs.{lvl}.bias'], 2, 0, out=cats[lvl + 1][:, :2 * chan])
-        sv_levels.append((sv_f, sv_e, x))
-        chan *= 2
-    cat = cats[n_enc]
-    x, sv_fm = naf_seq_fwd(cat, P, 'masa_blk_middle.0.', cfg['reffusion_n_blocks'][n_enc], c_out_last=chan)
-    x, sv_m = naf_seq_fwd(x, P, 'middle_blks.', cfg['middle_blk_num'])
-    sv_dec = []
-    for lvl in range(len(cfg['dec_blk_nums'])):
-        xin = x
-        x = up_fwd(xin, P[f'ups.{lvl}.0.weight'], skips[-1 - lvl])
-        x, sv_d = naf_seq_fwd(x, P, f'decoders.{lvl}.', cfg['dec_blk_nums'][lvl])
-        sv_dec.append((xin, sv_d))
-    xe = x
-    out_p = conv_fwd(xe, P['ending.weight'], P['ending.bias'], 1, 1, res=inp_p)
-    out = out_p if (Hp, Wp) == (H0, W0) else K.pad_crop(out_p, H0, W0)
-    saved = (N, (H0, W0, Hp, Wp), geo, pyr, None, None, sv_masa, warp, sv_levels, sv_fm, sv_m, sv_dec, xe)
-    return out, saved
+def _pad_into(src, dst_view):
+    """dst_view: dense [N,C,Hd,Wd] slice (contiguous along the batch)."""
+    N, Cc, Hs, Ws = src.shape
+    _, _, Hd, Wd = dst_view.shape
+    if (Hs, Ws) == (Hd, Wd):
+        K.copy_rows(src, Cc * Hs * Ws, dst_view, Cc * Hd * Wd, N, Cc * Hs * Ws)
+    else:
+        tmp = K.pad_crop(src, Hd, Wd)
+        K.copy_rows(tmp, Cc * Hd * Wd, dst_view, Cc * Hd * Wd, N, Cc * Hd * Wd)
 
 
-# ---------------------------------------------------------------------------- un-guided NAFNet (reference :305-386)
+# ---------------------------------------------------------------------------- TLSC (NAFNetLocal :756-768)
 def tlsc_kernel_sizes(cfg, train_size):
     """pooling kernel of every U-Net level as `Local_Base.convert` fixes it (nafnet_local_arch.py:29-36,99-104, NAFNetLocal :756-768):
     the first forward runs on rand(train_size) with base_size = int(1.5 x train size), and each AvgPool2d keeps
@@ -851,122 +825,134 @@ def tlsc_kernel_sizes(cfg, train_size):
     return [((Hp >> l) * bh // Ht, (Wp >> l) * bw // Wt) for l in range(n_enc + 1)]
 
 
-def unet_fwd(P, cfg, inp, local=None):
-    """`NAFNet.forward`: check_image_size (zero pad to a multiple of 2^len(encoders)) -> intro -> encoders / downs -> middle ->
-    ups (+ skip) / decoders -> ending + inp -> crop.  Same block kernels as the guided network, no reference branch.
-    local: per-level TLSC pooling kernels (tlsc_kernel_sizes) -- `NAFNetLocal`, inference only (saved state is empty)."""
+# ---------------------------------------------------------------------------
+# whole network: ONE walk of the NAFNet U-Net.  NAFNetRefFusion.forward (:587-740), NAFNet.forward (:305-386) and
+# NAFNetDynamicFusion.forward (dynfusion_engine) differ only by the arguments their callers below pass
+# ---------------------------------------------------------------------------
+def _level(cfg, l):
+    """(block prefix, block count, fusion-block prefix) of U-Net level l; l == len(enc_blk_nums) is the middle"""
+    if l == len(cfg['enc_blk_nums']):
+        return 'middle_blks.', cfg['middle_blk_num'], 'masa_blk_middle.0.'
+    return f'encoders.{l}.', cfg['enc_blk_nums'][l], f'masa_blk_enc.{l}.'
+
+
+def walk_fwd(P, cfg, inp, ref=None, seq=naf_seq_fwd, local=None):
+    """inp [N,3,H,W] -> (out [N,3,H,W], saved): zero pad -> intro -> encoders / downs -> middle -> ups (+ skip) / decoders ->
+    ending + inp -> crop.  cfg: constructor kwargs.
+    ref [N,3,Hr,Wr]: guided -- MASA pyramids and match (pyramids_fwd / masa_fwd), padding to the MASA block grid, and at every level
+    the fusion blocks `masa_blk_*` on cat[x, warp_l], then the first half of the channels (:719,727).  ref None: no reference
+    branch, padding to a multiple of 2^len(encoders) (check_image_size).
+    seq(x, P, prefix, n) -> (x, saved): the block sequence of a stage (`encoders.{l}.`, `middle_blks.`, `decoders.{l}.`)
+    local: per-level TLSC pooling kernels (tlsc_kernel_sizes), handed to seq -- `NAFNetLocal`, inference only (nothing saved)
+    saved = (N, (H0, W0, Hp, Wp), geo, pyr, None, None, sv_masa, S) -- geo, sv_masa None without a reference; S holds the rest by
+    name.  restormer_engine.walk_fwd saves the same prefix."""
     n_enc = len(cfg['enc_blk_nums'])
     N, _, H0, W0 = inp.shape
-    mult = 1 << n_enc
-    Hp, Wp = -(-H0 // mult) * mult, -(-W0 // mult) * mult
-    inp_p = inp.contiguous() if (Hp, Wp) == (H0, W0) else K.pad_crop(inp.contiguous(), Hp, Wp)
-    x = conv_fwd(inp_p, P['intro.weight'], P['intro.bias'], 1, 1)
-    sv_levels, skips = [], []
-    for lvl in range(n_enc):
-        x, sv_e = naf_seq_fwd(x, P, f'encoders.{lvl}.', cfg['enc_blk_nums'][lvl], local=local[lvl] if local else None)
-        skips.append(x)
-        sv_levels.append((sv_e, x))
-        x = conv_fwd(x, P[f'downs.{lvl}.weight'], P[f'downs.{lvl}.bias'], 2, 0)
-    x, sv_m = naf_seq_fwd(x, P, 'middle_blks.', cfg['middle_blk_num'], local=local[n_enc] if local else None)
-    sv_dec = []
-    for lvl in range(len(cfg['dec_blk_nums'])):
+    chan = P['intro.weight'].shape[0]
+    cats = sv_masa = None
+    if ref is not None:
+        pyr, sizes = pyramids_fwd(P, cfg, inp, ref, n_enc, n_enc + 1)
+        Hp, Wp = sizes[2:]
+        # cat([x, warp], 1) of every fusion level without copies: the transfer kernel writes the warped reference features
+        # (nf * 2^l channels) into the second half of the level's concat buffer, the conv that produces x writes the first half
+        cats = [torch.empty(N, (chan << l) + pyr.ref_feats[l].shape[1], Hp >> l, Wp >> l, dtype=torch.float32, device=inp.device)
+                for l in range(n_enc + 1)]
+        _, sv_masa = masa_fwd(pyr.lq_deep, pyr.ref_feats, N, pyr.geo, outs=[c[:, chan << l:] for l, c in enumerate(cats)])
+    else:
+        mult = 1 << n_enc
+        Hp, Wp = -(-H0 // mult) * mult, -(-W0 // mult) * mult
+        sizes = (H0, W0, Hp, Wp)
+        pyr = types.SimpleNamespace(inp_p=inp.contiguous() if (Hp, Wp) == (H0, W0) else K.pad_crop(inp.contiguous(), Hp, Wp), geo=None)
+
+    def stage(x, pre, n, l):
+        return seq(x, P, pre, n) if local is None else seq(x, P, pre, n, local=local[l])
+    S = types.SimpleNamespace(levels=[], dec=[])
+    x = conv_fwd(pyr.inp_p, P['intro.weight'], P['intro.bias'], 1, 1, out=cats[0][:, :chan] if cats else None)
+    for l in range(n_enc + 1):
+        pre, n, fus = _level(cfg, l)
+        sv_f = None
+        if cats:
+            x, sv_f = naf_seq_fwd(cats[l], P, fus, cfg['reffusion_n_blocks'][l], c_out_last=chan << l)
+        x, sv_e = stage(x, pre, n, l)
+        S.levels.append((sv_f, sv_e, x))                   # x: the skip, and what downs.{l} reads
+        if l < n_enc:
+            x = conv_fwd(x, P[f'downs.{l}.weight'], P[f'downs.{l}.bias'], 2, 0, out=cats[l + 1][:, :chan << (l + 1)] if cats else None)
+    for l in range(len(cfg['dec_blk_nums'])):
         xin = x
-        x = up_fwd(xin, P[f'ups.{lvl}.0.weight'], skips[-1 - lvl])
-        x, sv_d = naf_seq_fwd(x, P, f'decoders.{lvl}.', cfg['dec_blk_nums'][lvl], local=local[n_enc - 1 - lvl] if local else None)
-        sv_dec.append((xin, sv_d))
-    out_p = conv_fwd(x, P['ending.weight'], P['ending.bias'], 1, 1, res=inp_p)
+        x = up_fwd(xin, P[f'ups.{l}.0.weight'], S.levels[n_enc - 1 - l][2])
+        x, sv_d = stage(x, f'decoders.{l}.', cfg['dec_blk_nums'][l], n_enc - 1 - l)
+        S.dec.append((xin, sv_d))
+    S.xe = x
+    out_p = conv_fwd(x, P['ending.weight'], P['ending.bias'], 1, 1, res=pyr.inp_p)
     out = out_p if (Hp, Wp) == (H0, W0) else K.pad_crop(out_p, H0, W0)
-    return out, ((H0, W0, Hp, Wp), inp_p, sv_levels, sv_m, sv_dec, x)
+    return out, (N, sizes, pyr.geo, pyr, None, None, sv_masa, S)
 
 
-def unet_bwd(dout, P, cfg, saved, G=None):
-    """-> (dinp, G): gradient w.r.t. the input image (the `+ inp` skip and the intro conv) and every parameter"""
-    with deferred_join():
-        (H0, W0, Hp, Wp), inp_p, sv_levels, sv_m, sv_dec, xe = saved
-        n_enc = len(cfg['enc_blk_nums'])
-        G = {} if G is None else G
+def walk_bwd(dout, P, cfg, saved, G=None, seq=naf_seq_bwd):
+    """dout [N,3,H0,W0] -> (dinp, G): the parameter gradients of walk_fwd keyed like P, and the gradient w.r.t. the input image
+    (the `+ inp` skip and the intro conv) -- None for the guided network, whose image is data.
+    `G` may be a caller's dict-like collector (e.g. parallel.GradSink, which starts the RCCL all-reduce of a gradient bucket as
+    soon as its last tensor is stored): the order of the stores is behaviour.
+    seq(d, P, prefix, n, saved, G) -> d: the backward of walk_fwd's seq.
+    Guided: leaf weight gradients are queued (late_leaves; per level with a gradient exchange, level_end) and run next to the MASA
+    backward at the end (run_late_leaves).  Un-guided: they run at once -- grouped 1x1 weight gradients are not bit-identical to
+    ungrouped ones (see restormer_engine.net_bwd)."""
+    G = {} if G is None else G
+    N, (H0, W0, Hp, Wp), _, pyr, _, _, sv_masa, S = saved[:8]
+    guided = sv_masa is not None
+    n_enc = len(cfg['enc_blk_nums'])
+    chan = P['intro.weight'].shape[0]
+    with deferred_join(), (late_leaves(G, level_ok=True) if guided else contextlib.nullcontext()):
         dout = dout.contiguous()
         if (Hp, Wp) != (H0, W0):
             dout = K.pad_crop(dout, Hp, Wp)
-        d, _, _ = conv_bwd(dout, xe, P['ending.weight'], 1, 1, into=(G, 'ending.weight', 'ending.bias'))
+        # ending conv (the `+ inp` residual has no parameter gradient)
+        d, G['ending.weight'], G['ending.bias'] = conv_bwd(dout, S.xe, P['ending.weight'], 1, 1)
         dskips = [None] * n_enc
-        for lvl in reversed(range(len(cfg['dec_blk_nums']))):
-            xin, sv_d = sv_dec[lvl]
-            d = naf_seq_bwd(d, P, f'decoders.{lvl}.', cfg['dec_blk_nums'][lvl], sv_d, G)
-            dskips[n_enc - 1 - lvl] = d
-            d, G[f'ups.{lvl}.0.weight'] = up_bwd(d, xin, P[f'ups.{lvl}.0.weight'])
-        d = naf_seq_bwd(d, P, 'middle_blks.', cfg['middle_blk_num'], sv_m, G)
-        for lvl in reversed(range(n_enc)):
-            sv_e, x_skip = sv_levels[lvl]
-            d, G[f'downs.{lvl}.weight'], G[f'downs.{lvl}.bias'] = conv_bwd(d, x_skip, P[f'downs.{lvl}.weight'], 2, 0,
-                                                                          add_to_dx=dskips[lvl])
-            d = naf_seq_bwd(d, P, f'encoders.{lvl}.', cfg['enc_blk_nums'][lvl], sv_e, G)
-        dinp, G['intro.weight'], G['intro.bias'] = conv_bwd(d, inp_p, P['intro.weight'], 1, 1, need_dx=True, add_to_dx=dout)
-        if (Hp, Wp) != (H0, W0):
+        for l in reversed(range(len(cfg['dec_blk_nums']))):
+            xin, sv_d = S.dec[l]
+            d = seq(d, P, f'decoders.{l}.', cfg['dec_blk_nums'][l], sv_d, G)
+            level_end(G)
+            dskips[n_enc - 1 - l] = d                      # gradient of `x + enc_skip` w.r.t. the skip
+            d, _ = up_bwd(d, xin, P[f'ups.{l}.0.weight'], into=(G, f'ups.{l}.0.weight'))
+        dwarp = [None] * (n_enc + 1)
+        for l in reversed(range(n_enc + 1)):
+            pre, n, fus = _level(cfg, l)
+            sv_f, sv_e, x_skip = S.levels[l]
+            if l < n_enc:
+                # downs: gradient into the skip tensor, accumulated with the decoder-side skip gradient
+                d, _, _ = conv_bwd(d, x_skip, P[f'downs.{l}.weight'], 2, 0, add_to_dx=dskips[l],
+                                   into=(G, f'downs.{l}.weight', f'downs.{l}.bias'))
+            d = seq(d, P, pre, n, sv_e, G)
+            if guided:
+                dcat = naf_seq_bwd(d, P, fus, cfg['reffusion_n_blocks'][l], sv_f, G)
+                level_end(G)
+                dwarp[l] = dcat[:, chan << l:]
+                d = dcat[:, :chan << l]                    # batch-strided view: every consumer takes an image stride
+        dinp, _, _ = conv_bwd(d, pyr.inp_p, P['intro.weight'], 1, 1, need_dx=not guided, add_to_dx=None if guided else dout,
+                              into=(G, 'intro.weight', 'intro.bias'))
+        if dinp is not None and (Hp, Wp) != (H0, W0):
             dinp = K.pad_crop(dinp, H0, W0)
-        return dinp, G
+        if guided:
+            run_late_leaves(G, lambda: pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G))
+    return dinp, G
 
 
-def _pad_into(src, dst_view):
-    """dst_view: dense [N,C,Hd,Wd] slice (contiguous along the batch)."""
-    N, Cc, Hs, Ws = src.shape
-    _, _, Hd, Wd = dst_view.shape
-    if (Hs, Ws) == (Hd, Wd):
-        K.copy_rows(src, Cc * Hs * Ws, dst_view, Cc * Hd * Wd, N, Cc * Hs * Ws)
-    else:
-        tmp = K.pad_crop(src, Hd, Wd)
-        K.copy_rows(tmp, Cc * Hd * Wd, dst_view, Cc * Hd * Wd, N, Cc * Hd * Wd)
+def net_fwd(P, cfg, inp, ref):
+    """NAFNetRefFusion: inp, ref [N,3,H,W] -> (out [N,3,H,W], saved)"""
+    return walk_fwd(P, cfg, inp, ref)
 
 
 def net_bwd(dout, P, cfg, saved, G=None):
-    """dout [N,3,H0,W0] -> dict of parameter gradients keyed like P.  `G` may be a caller's
-    dict-like collector (e.g. parallel.GradSink, which starts the RCCL all-reduce of a
-    gradient bucket as soon as its last tensor is stored)."""
-    with deferred_join():
-        return _net_bwd(dout, P, cfg, saved, G)
+    """-> G, the parameter gradients (the input image is data)"""
+    return walk_bwd(dout, P, cfg, saved, G)[1]
 
 
-def _net_bwd(dout, P, cfg, saved, G):
-    G = {} if G is None else G
-    with late_leaves(G, level_ok=True):
-        return _net_bwd_body(dout, P, cfg, saved, G)
+def unet_fwd(P, cfg, inp, local=None):
+    """`NAFNet.forward`; local: `NAFNetLocal` (TLSC inference)"""
+    return walk_fwd(P, cfg, inp, local=local)
 
 
-def _net_bwd_body(dout, P, cfg, saved, G):
-    N, (H0, W0, Hp, Wp), geo, pyr, _, _, sv_masa, warp, sv_levels, sv_fm, sv_m, sv_dec, xe = saved
-    n_enc = len(cfg['enc_blk_nums'])
-    inp_p = pyr.inp_p
-    dout = dout.contiguous()
-    if (Hp, Wp) != (H0, W0):
-        dout = K.pad_crop(dout, Hp, Wp)
-    # ending conv (+inp residual has no parameter gradient)
-    d, G['ending.weight'], G['ending.bias'] = conv_bwd(dout, xe, P['ending.weight'], 1, 1)
-    dskips = [None] * n_enc
-    for lvl in reversed(range(len(cfg['dec_blk_nums']))):
-        xin, sv_d = sv_dec[lvl]
-        d = naf_seq_bwd(d, P, f'decoders.{lvl}.', cfg['dec_blk_nums'][lvl], sv_d, G)
-        level_end(G)
-        dskips[n_enc - 1 - lvl] = d                    # gradient of `x + enc_skip` w.r.t. the skip
-        d, _ = up_bwd(d, xin, P[f'ups.{lvl}.0.weight'], into=(G, f'ups.{lvl}.0.weight'))
-    d = naf_seq_bwd(d, P, 'middle_blks.', cfg['middle_blk_num'], sv_m, G)
-    dcat = naf_seq_bwd(d, P, 'masa_blk_middle.0.', cfg['reffusion_n_blocks'][n_enc], sv_fm, G)
-    level_end(G)
-    dwarp = [None] * 5
-    chan = dcat.shape[1] // 2
-    dwarp[n_enc] = dcat[:, chan:]
-    d = dcat[:, :chan]                                 # batch-strided view: every consumer takes an image stride
-    for lvl in reversed(range(n_enc)):
-        sv_f, sv_e, x_skip = sv_levels[lvl]
-        # downs: gradient into the skip tensor, accumulated with the decoder-side skip gradient
-        d, _, _ = conv_bwd(d, x_skip, P[f'downs.{lvl}.weight'], 2, 0, add_to_dx=dskips[lvl],
-                           into=(G, f'downs.{lvl}.weight', f'downs.{lvl}.bias'))
-        d = naf_seq_bwd(d, P, f'encoders.{lvl}.', cfg['enc_blk_nums'][lvl], sv_e, G)
-        dcat = naf_seq_bwd(d, P, f'masa_blk_enc.{lvl}.', cfg['reffusion_n_blocks'][lvl], sv_f, G)
-        level_end(G)
-        chan = dcat.shape[1] // 2
-        dwarp[lvl] = dcat[:, chan:]
-        d = dcat[:, :chan]                             # batch-strided view: every consumer takes an image stride
-    # intro conv: input image needs no gradient
-    conv_bwd(d, inp_p, P['intro.weight'], 1, 1, need_dx=False, into=(G, 'intro.weight', 'intro.bias'))
-    run_late_leaves(G, lambda: pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G))
-    return G
+def unet_bwd(dout, P, cfg, saved, G=None):
+    """-> (dinp, G)"""
+    return walk_bwd(dout, P, cfg, saved, G)
