@@ -726,6 +726,10 @@ typedef struct TdrNafTailDesc {
 } TdrNafTailDesc;
 int tdr_naf_tail_supported(int C, int HW);
 int tdr_naf_tail_fwd(const TdrNafTailDesc* d, void* stream);
+/* The same chain for a forward pass that keeps nothing (inference): only `out` is written.  y, mu, rs, yn and t4 must be NULL (their
+ * strides are ignored).  Same kernel body with those stores compiled out -- tile shape, wave count, MFMA sequence, reduction order
+ * and support are tdr_naf_tail_fwd's, so `out` is bit-identical to it in every arithmetic. */
+int tdr_naf_tail_infer(const TdrNafTailDesc* d, void* stream);
 /* Data-gradient chain of the same half (autograd of :230-238), one launch instead of three:
  *   dt4 = SimpleGate'(W5^T (dout * gamma); t4);  dyn = W4^T dt4;  dy = LayerNorm2d'(dyn; y, mu, rs, lnw) + dout
  * plus the LayerNorm parameter gradients gw = sum dyn * yhat, gb = sum dyn (per-workgroup partials in ws, reduced in a
@@ -768,6 +772,8 @@ typedef struct TdrNafHeadFwdDesc {
     float* t1; int64_t t1_ns;                /* [N, 2C, HW] */
 } TdrNafHeadFwdDesc;
 int tdr_naf_head_fwd(const TdrNafHeadFwdDesc* d, void* stream);
+/* Forward-only variant: only t1 is written; mu, rs and xn must be NULL.  t1 is bit-identical to tdr_naf_head_fwd's. */
+int tdr_naf_head_infer(const TdrNafHeadFwdDesc* d, void* stream);
 /* The first half's data gradients (autograd of :216-225 from conv1 back), one launch instead of two:
  *   dxn = W1^T dt1;  dx = LayerNorm2d'(dxn; x, mu, rs, lnw) + res        (res = gradient of the `inp + ...` skip)
  * plus norm1's parameter gradients.  w1t: tdr_pack_weights_hx2(mode DGRAD_S1) of conv1 (2C x C).  Same support / ws. */

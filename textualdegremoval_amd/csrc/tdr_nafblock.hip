@@ -199,7 +199,10 @@ struct TailArgs {
 // 2C threads = C/32 waves (C = 256: 8 waves, two per SIMD): wave w owns the 32 channels [32w, 32w + 32) of the C-row GEMMs and, in conv4,
 // also their SimpleGate partners [C + 32w, C + 32w + 32).  While one wave of a SIMD waits on LDS / L2 / the store
 // queue its partner's MFMAs run.
-template <int C, int SCH>
+// KEEP = false is the forward-only chain (tdr_naf_tail_infer): the stores of y, yn, t4, mu and rs -- what only the backward pass reads --
+// are compiled out (their TailArgs fields are NULL) and `out` is the one tensor written.  Tiles, waves, MFMA sequence and reduction order
+// are those of KEEP = true, so `out` has the same bits.
+template <int C, bool KEEP, int SCH>
 __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
     static_assert(C == 256 || C == 128 || C == 64 || C == 32, "C / 32 waves x 32 channel rows");
     constexpr int NS = SchT<SCH>::NS;
@@ -308,9 +311,11 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
         const float* rp = red + NW * NPX + 32 * tn + j;
         const float var = wave_partials_sum<NW>(rp) * (1.f / C);
         rstd[tn] = 1.f / sqrtf(var + a.eps);
-        if (wave == 0 && kk == 0) {
-            a.mu[(long)n * HW + p0 + 32 * tn + j] = mean[tn];
-            a.rs[(long)n * HW + p0 + 32 * tn + j] = rstd[tn];
+        if constexpr (KEEP) {
+            if (wave == 0 && kk == 0) {
+                a.mu[(long)n * HW + p0 + 32 * tn + j] = mean[tn];
+                a.rs[(long)n * HW + p0 + 32 * tn + j] = rstd[tn];
+            }
         }
     }
     // yn = (y - mu) * rstd * w + b : split into the LDS operand now; y and yn leave for HBM under conv4's MFMAs
@@ -327,7 +332,7 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) ynv[tn][r] = (yv[tn][r] - mean[tn]) * rstd[tn] * lw[r] + lb[r];
             tile_to_planes<SCH>(ynv[tn], sB, NOCT, 4 * wave, 32 * tn + j, kk);
-            if constexpr (EARLY_STORES) {
+            if constexpr (KEEP && EARLY_STORES) {
                 float* yp = a.y + (long)n * a.y_ns + p0 + j;
                 float* ynp = a.yn + (long)n * a.yn_ns + p0 + j;
 #pragma unroll
@@ -350,11 +355,11 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc4[tm][tn][r] = 0.f;
     {
-        float* yp = a.y + (long)n * a.y_ns + p0 + j;
-        float* ynp = a.yn + (long)n * a.yn_ns + p0 + j;
+        float* yp = KEEP ? a.y + (long)n * a.y_ns + p0 + j : nullptr;         // (no arithmetic on the NULL fields of the forward-only chain)
+        float* ynp = KEEP ? a.yn + (long)n * a.yn_ns + p0 + j : nullptr;
         gemm_split<SCH, 2, NG, 2>(acc4, a.w4, 2 * C / 32, [&](int tm) { return tm * (C / 32) + wave; }, sB, NOCT, lane, rot, [&](int g) {
             // 64 dword stores (y, yn: 2 sub-tiles x 16 rows each) spread evenly over the NG groups
-            if constexpr (EARLY_STORES) return;
+            if constexpr (!KEEP || EARLY_STORES) return;
             constexpr int IPG = 32 / NG;
 #pragma unroll
             for (int e = 0; e < IPG; ++e) {
@@ -395,8 +400,8 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
 
     // ---- conv5: out = (W5 gate + b5) * gamma + y ; the t4 tile leaves for HBM under its MFMAs.  Only the first c_out rows
     // exist (fusion blocks keep `[:, :chan]`): the waves above them just store their t4 tiles.
-    float* tp = a.t4 + (long)n * a.t4_ns + p0 + j;
-    if constexpr (EARLY_STORES) {
+    float* tp = KEEP ? a.t4 + (long)n * a.t4_ns + p0 + j : nullptr;
+    if constexpr (KEEP && EARLY_STORES) {
 #pragma unroll
         for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -410,7 +415,7 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[0][tn][r] = 0.f;
         gemm_split<SCH, 1, NG, 2>(acc, a.w5, a.c_out / 32, [&](int) { return wave; }, sB, NOCT, lane, rot, [&](int g) {
-            if constexpr (EARLY_STORES) return;
+            if constexpr (!KEEP || EARLY_STORES) return;
             constexpr int IPG = 64 / NG;                                         // 64 stores spread evenly over the NG groups
 #pragma unroll
             for (int e = 0; e < IPG; ++e) {
@@ -425,7 +430,7 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) op[off(r, tn)] = (acc[0][tn][r] + b5v[r]) * gav[r] + yv[tn][r];
         NB_STAMP(7);
-    } else if constexpr (!EARLY_STORES) {
+    } else if constexpr (KEEP && !EARLY_STORES) {
 #pragma unroll
         for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -453,7 +458,8 @@ struct HeadFwdArgs {
     int HW;
 };
 
-template <int C, int SCH>
+// KEEP = false (tdr_naf_head_infer): xn, mu and rs stay on the chip (NULL in HeadFwdArgs), t1 is the one tensor written -- same bits.
+template <int C, bool KEEP, int SCH>
 __global__ __launch_bounds__(2 * C, 2) void naf_head_fwd_kernel(HeadFwdArgs a) {
     constexpr int NOCT = C / 8, NG = C / 16, NW = C / 32, NS = SchT<SCH>::NS;
     extern __shared__ __attribute__((aligned(16))) uint4 smem4[];
@@ -507,9 +513,11 @@ __global__ __launch_bounds__(2 * C, 2) void naf_head_fwd_kernel(HeadFwdArgs a) {
     for (int tn = 0; tn < 2; ++tn) {
         const float var = wave_partials_sum<NW>(red + NW * NPX + 32 * tn + j) * (1.f / C);
         rstd[tn] = 1.f / sqrtf(var + a.eps);
-        if (wave == 0 && kk == 0) {
-            a.mu[(long)n * HW + p0 + 32 * tn + j] = mean[tn];
-            a.rs[(long)n * HW + p0 + 32 * tn + j] = rstd[tn];
+        if constexpr (KEEP) {
+            if (wave == 0 && kk == 0) {
+                a.mu[(long)n * HW + p0 + 32 * tn + j] = mean[tn];
+                a.rs[(long)n * HW + p0 + 32 * tn + j] = rstd[tn];
+            }
         }
     }
     float xnv[2][16];
@@ -538,8 +546,9 @@ __global__ __launch_bounds__(2 * C, 2) void naf_head_fwd_kernel(HeadFwdArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
     {
-        float* xnp = a.xn + (long)n * a.xn_ns + p0 + j;
+        float* xnp = KEEP ? a.xn + (long)n * a.xn_ns + p0 + j : nullptr;
         gemm_split<SCH, 2, NG, 2>(acc, a.w1, 2 * C / 32, [&](int tm) { return tm * (C / 32) + wave; }, sB, NOCT, lane, rot, [&](int g) {
+            if constexpr (!KEEP) return;
             constexpr int IPG = 32 / NG;
 #pragma unroll
             for (int e = 0; e < IPG; ++e) {
@@ -880,16 +889,6 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_bwd_kernel(TailBwdArgs a) {
     }
 }
 
-}  // namespace
-
-#ifdef TDR_NB_PROBE
-extern "C" int tdr_nb_probe_read(unsigned long long* host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(nb_probe_buf), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;
-}
-#endif
-
-extern "C" int tdr_naf_tail_supported(int C, int HW) { return ((C == 256 || C == 128 || C == 64 || C == 32) && HW % 64 == 0) ? 1 : 0; }
-
 #define NAF_DISPATCH_C(C_, KERNEL_EXPR, lds_, a_, d_, stream_)                                                                   \
     do {                                                                                                                         \
         auto kern = KERNEL_EXPR;                                                                                                 \
@@ -918,13 +917,20 @@ extern "C" int tdr_naf_tail_supported(int C, int HW) { return ((C == 256 || C ==
         }                                                                                                            \
     } while (0)
 
-extern "C" int tdr_naf_tail_fwd(const TdrNafTailDesc* d, void* stream) {
+static bool naf_chain_supported(int C, int HW) { return (C == 256 || C == 128 || C == 64 || C == 32) && HW % 64 == 0; }
+
+// tdr_naf_tail_fwd (KEEP: y, mu, rs, yn, t4 are outputs) and tdr_naf_tail_infer (!KEEP: those fields must be NULL, nothing is written there)
+template <bool KEEP>
+static int naf_tail_fwd_launch(const TdrNafTailDesc* d, void* stream) {
+    const char* fn = KEEP ? "tdr_naf_tail_fwd" : "tdr_naf_tail_infer";
     TDR_REQUIRE(d && d->g && d->sca && d->x && d->w3 && d->w4 && d->w5 && d->b3 && d->beta && d->lnw && d->lnb && d->b4 && d->b5 &&
-                    d->gamma && d->y && d->mu && d->rs && d->yn && d->t4 && d->out,
-                "tdr_naf_tail_fwd: null pointer");
-    TDR_REQUIRE(tdr_naf_tail_supported(d->C, d->HW), "tdr_naf_tail_fwd: needs C in {32, 64, 128, 256} and HW %% 64 == 0 (got C=%d HW=%d)", d->C, d->HW);
-    TDR_REQUIRE(d->w_fmt == 2 || d->w_fmt == 1, "tdr_naf_tail_fwd: weights must be packed with tdr_pack_weights_hx2 / _bx3 (mode FWD)");
-    TDR_REQUIRE(d->HW % 4 == 0 && d->g_ns % 4 == 0 && (reinterpret_cast<uintptr_t>(d->g) & 15) == 0, "tdr_naf_tail_fwd: g must be 16-byte aligned");
+                    d->gamma && d->out,
+                "%s: null pointer", fn);
+    if (KEEP) TDR_REQUIRE(d->y && d->mu && d->rs && d->yn && d->t4, "%s: null pointer", fn);
+    else TDR_REQUIRE(!d->y && !d->mu && !d->rs && !d->yn && !d->t4, "%s: y, mu, rs, yn and t4 are not written and must be NULL", fn);
+    TDR_REQUIRE(naf_chain_supported(d->C, d->HW), "%s: needs C in {32, 64, 128, 256} and HW %% 64 == 0 (got C=%d HW=%d)", fn, d->C, d->HW);
+    TDR_REQUIRE(d->w_fmt == 2 || d->w_fmt == 1, "%s: weights must be packed with tdr_pack_weights_hx2 / _bx3 (mode FWD)", fn);
+    TDR_REQUIRE(d->HW % 4 == 0 && d->g_ns % 4 == 0 && (reinterpret_cast<uintptr_t>(d->g) & 15) == 0, "%s: g must be 16-byte aligned", fn);
     TailArgs a;
     a.g = d->g; a.g_ns = d->g_ns; a.sca = d->sca; a.x = d->x; a.x_ns = d->x_ns;
     a.w3 = reinterpret_cast<const uint4*>(d->w3); a.w4 = reinterpret_cast<const uint4*>(d->w4); a.w5 = reinterpret_cast<const uint4*>(d->w5);
@@ -933,28 +939,52 @@ extern "C" int tdr_naf_tail_fwd(const TdrNafTailDesc* d, void* stream) {
     a.y = d->y; a.y_ns = d->y_ns; a.mu = d->mu; a.rs = d->rs; a.yn = d->yn; a.yn_ns = d->yn_ns; a.t4 = d->t4; a.t4_ns = d->t4_ns;
     a.out = d->out; a.out_ns = d->out_ns; a.HW = d->HW;
     a.c_out = d->c_out > 0 ? d->c_out : d->C;
-    TDR_REQUIRE(a.c_out == d->C || (a.c_out * 2 == d->C && a.c_out % 32 == 0), "tdr_naf_tail_fwd: c_out must be C or C / 2 (a multiple of 32)");
+    TDR_REQUIRE(a.c_out == d->C || (a.c_out * 2 == d->C && a.c_out % 32 == 0), "%s: c_out must be C or C / 2 (a multiple of 32)", fn);
     const bool bx = d->w_fmt == 1;
     const size_t lds = (size_t)(bx ? 3 : 2) * (d->C / 8) * NPX * 16 + (size_t)2 * (d->C / 32) * NPX * sizeof(float);      // planes + red[2][C / 32 waves][64 px]
-    NAF_DISPATCH_CS(naf_tail_fwd_kernel, , lds, a, d, stream);
-    TDR_LAUNCH_CHECK("naf_tail_fwd_kernel");
+    NAF_DISPATCH_CS(naf_tail_fwd_kernel, NAF_COMMA KEEP, lds, a, d, stream);
+    TDR_LAUNCH_CHECK(KEEP ? "naf_tail_fwd_kernel" : "naf_tail_fwd_kernel<infer>");
     return TDR_OK;
 }
 
-extern "C" int tdr_naf_head_fwd(const TdrNafHeadFwdDesc* d, void* stream) {
-    TDR_REQUIRE(d && d->x && d->lnw && d->lnb && d->w1 && d->b1 && d->mu && d->rs && d->xn && d->t1, "tdr_naf_head_fwd: null pointer");
-    TDR_REQUIRE(tdr_naf_tail_supported(d->C, d->HW), "tdr_naf_head_fwd: needs C in {32, 64, 128, 256} and HW %% 64 == 0 (got C=%d HW=%d)", d->C, d->HW);
-    TDR_REQUIRE(d->w_fmt == 2 || d->w_fmt == 1, "tdr_naf_head_fwd: weights must be packed with tdr_pack_weights_hx2 / _bx3 (mode FWD)");
+// tdr_naf_head_fwd (KEEP: mu, rs, xn are outputs) and tdr_naf_head_infer (!KEEP: they must be NULL)
+template <bool KEEP>
+static int naf_head_fwd_launch(const TdrNafHeadFwdDesc* d, void* stream) {
+    const char* fn = KEEP ? "tdr_naf_head_fwd" : "tdr_naf_head_infer";
+    TDR_REQUIRE(d && d->x && d->lnw && d->lnb && d->w1 && d->b1 && d->t1, "%s: null pointer", fn);
+    if (KEEP) TDR_REQUIRE(d->mu && d->rs && d->xn, "%s: null pointer", fn);
+    else TDR_REQUIRE(!d->mu && !d->rs && !d->xn, "%s: mu, rs and xn are not written and must be NULL", fn);
+    TDR_REQUIRE(naf_chain_supported(d->C, d->HW), "%s: needs C in {32, 64, 128, 256} and HW %% 64 == 0 (got C=%d HW=%d)", fn, d->C, d->HW);
+    TDR_REQUIRE(d->w_fmt == 2 || d->w_fmt == 1, "%s: weights must be packed with tdr_pack_weights_hx2 / _bx3 (mode FWD)", fn);
     HeadFwdArgs a;
     a.x = d->x; a.x_ns = d->x_ns; a.lnw = d->lnw; a.lnb = d->lnb; a.eps = d->eps;
     a.w1 = reinterpret_cast<const uint4*>(d->w1); a.b1 = d->b1;
     a.mu = d->mu; a.rs = d->rs; a.xn = d->xn; a.xn_ns = d->xn_ns; a.t1 = d->t1; a.t1_ns = d->t1_ns; a.HW = d->HW;
     const bool bx = d->w_fmt == 1;
     const size_t lds = (size_t)(bx ? 3 : 2) * (d->C / 8) * NPX * 16 + (size_t)2 * (d->C / 32) * NPX * sizeof(float);      // planes + red[2][C / 32 waves][64 px]
-    NAF_DISPATCH_CS(naf_head_fwd_kernel, , lds, a, d, stream);
-    TDR_LAUNCH_CHECK("naf_head_fwd_kernel");
+    NAF_DISPATCH_CS(naf_head_fwd_kernel, NAF_COMMA KEEP, lds, a, d, stream);
+    TDR_LAUNCH_CHECK(KEEP ? "naf_head_fwd_kernel" : "naf_head_fwd_kernel<infer>");
     return TDR_OK;
 }
+
+}  // namespace
+
+// The forward-only instantiations are a translation unit of their own (tdr_nafblock_infer.hip includes this file with TDR_NAF_INFER_TU
+// defined), so that this file's object holds the training kernels and nothing else.  Compiled in one unit the training kernels come
+// out the same and the forward-only ones do not (profiles/probe_infer_isa.py); the ones tested and measured are the separate unit's.
+#ifdef TDR_NAF_INFER_TU
+extern "C" int tdr_naf_tail_infer(const TdrNafTailDesc* d, void* stream) { return naf_tail_fwd_launch<false>(d, stream); }
+extern "C" int tdr_naf_head_infer(const TdrNafHeadFwdDesc* d, void* stream) { return naf_head_fwd_launch<false>(d, stream); }
+#else
+#ifdef TDR_NB_PROBE
+extern "C" int tdr_nb_probe_read(unsigned long long* host) {
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(nb_probe_buf), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;
+}
+#endif
+
+extern "C" int tdr_naf_tail_supported(int C, int HW) { return naf_chain_supported(C, HW) ? 1 : 0; }
+extern "C" int tdr_naf_tail_fwd(const TdrNafTailDesc* d, void* stream) { return naf_tail_fwd_launch<true>(d, stream); }
+extern "C" int tdr_naf_head_fwd(const TdrNafHeadFwdDesc* d, void* stream) { return naf_head_fwd_launch<true>(d, stream); }
 
 extern "C" int64_t tdr_naf_tail_bwd_ws_floats(int N, int C, int HW) {
     const int nparts = N * (HW / NPX);
@@ -1006,3 +1036,4 @@ extern "C" int tdr_naf_head_bwd(const TdrNafHeadBwdDesc* d, void* stream) {
     if (!d->gw) return TDR_OK;
     return tdr_pair_sum_partials(d->ws, d->N * (d->HW / NPX), d->C, d->gw, d->gb, d->ws + (long)d->N * (d->HW / NPX) * 2 * d->C, stream);
 }
+#endif  // !TDR_NAF_INFER_TU

@@ -24,6 +24,9 @@ LN_EPS = 1e-6
 FUSE_TAIL = True
 FUSE_HEAD = True                                                          # norm1 -> conv1 (forward)
 FUSE_CONV3_DGRAD = True                                                   # conv3's data gradient at the end of the tail backward
+# a forward pass that keeps nothing (keep=False) runs the forward-only chains tdr_naf_head_infer / tdr_naf_tail_infer; False: the training
+# chains, their saved tensors dropped on return (the A/B of profiles/probe_infer.py: what the kernels add to what the walk releases)
+INFER_KERNELS = True
 
 
 def _sub(P, pre):
@@ -260,35 +263,57 @@ def run_late_leaves(G, main_chain):
 # ---------------------------------------------------------------------------
 # NAFBlock / NAFResFuseBlock   models/archs/network_nafnet_guided_arch.py:178-302
 # ---------------------------------------------------------------------------
-def naf_fwd(x, P, c_out=None):
+def naf_fwd(x, P, c_out=None, keep=True):
     """x [N,c,H,W] -> [N,c_out,H,W] (c_out<c: only the first c_out output channels are
-    produced, the `[:, :chan]` slice of :719/:727 folded into conv5)."""
+    produced, the `[:, :chan]` slice of :719/:727 folded into conv5).
+    keep=False: a forward pass no backward follows -> (out, None).  The fused chains run their forward-only variants (the tensors only
+    naf_bwd reads never reach HBM; `out` has the same bits), the per-op launches are the same and every intermediate is dropped once its
+    last consumer is enqueued (same stream: the allocator hands the block to the next launch in stream order)."""
     N, c, H, W = x.shape
     c_out = c if c_out is None else c_out
+    lean = not keep and INFER_KERNELS
     wp, mp, *_ = K.pack_weights(P['conv1.weight'], PACK_FWD)
     if FUSE_HEAD and K.naf_tail_supported(c, H * W) and wp.fmt in (K.FMT_HX2, K.FMT_BX3):
         # norm1 -> conv1 in one launch (the workgroup that owns 64 pixels x all channels reduces the statistics itself)
-        xn, mu1, rs1, t1 = K.naf_head_fwd(x, P['norm1.weight'], P['norm1.bias'], LN_EPS, wp, P['conv1.bias'])
+        if lean:
+            xn = mu1 = rs1 = None
+            t1 = K.naf_head_infer(x, P['norm1.weight'], P['norm1.bias'], LN_EPS, wp, P['conv1.bias'])
+        else:
+            xn, mu1, rs1, t1 = K.naf_head_fwd(x, P['norm1.weight'], P['norm1.bias'], LN_EPS, wp, P['conv1.bias'])
     else:
         xn, mu1, rs1 = K.layernorm2d_fwd(x, P['norm1.weight'], P['norm1.bias'], LN_EPS)
         t1 = K.conv_forward(xn, wp, mp, 2 * c, 1, bias=P['conv1.bias'])
+    if not keep:
+        xn = mu1 = rs1 = None
     g, pooled = K.dwsg_fwd(t1, P['conv2.weight'], P['conv2.bias'])
+    if not keep:
+        t1 = None
     s = K.sca_fwd(pooled, P['sca.1.weight'], P['sca.1.bias'])
     if FUSE_TAIL and K.naf_tail_supported(c, H * W, c_out) and x.is_contiguous():
         # conv3 -> norm2 -> conv4 -> SimpleGate -> conv5 in one launch (one workgroup per 64 pixels x all channels)
         w3p, w4p = (K.pack_weights(P[k], PACK_FWD)[0] for k in ('conv3.weight', 'conv4.weight'))
         w5p = K.pack_weights(P['conv5.weight'][:c_out], PACK_FWD)[0]
-        out, y, mu2, rs2, yn, t4 = K.naf_tail_fwd(g, s, x, w3p, P['conv3.bias'], P['beta'].view(-1), P['norm2.weight'],
-                                                  P['norm2.bias'], LN_EPS, w4p, P['conv4.bias'], w5p, P['conv5.bias'],
-                                                  P['gamma'].view(-1), c_out=c_out)
+        args = (g, s, x, w3p, P['conv3.bias'], P['beta'].view(-1), P['norm2.weight'], P['norm2.bias'], LN_EPS, w4p, P['conv4.bias'],
+                w5p, P['conv5.bias'], P['gamma'].view(-1))
+        if lean:
+            return K.naf_tail_infer(*args, c_out=c_out), None
+        out, y, mu2, rs2, yn, t4 = K.naf_tail_fwd(*args, c_out=c_out)
+        if not keep:                                       # INFER_KERNELS off: the training chain ran, what it saved is dropped here
+            return out, None
         return out, (x, xn, mu1, rs1, t1, g, pooled, s, y, yn, mu2, rs2, t4, c_out)
     wp, mp, *_ = K.pack_weights(P['conv3.weight'], PACK_FWD)
     y = K.conv_forward(g, wp, mp, c, 1, kscale=s, bias=P['conv3.bias'], scale=P['beta'].view(-1), res=x)
+    if not keep:
+        g = None
     yn, mu2, rs2 = K.layernorm2d_fwd(y, P['norm2.weight'], P['norm2.bias'], LN_EPS)
     wp, mp, *_ = K.pack_weights(P['conv4.weight'], PACK_FWD)
     t4 = K.conv_forward(yn, wp, mp, 2 * c, 1, bias=P['conv4.bias'])
+    if not keep:
+        yn = None
     wp, mp, *_ = K.pack_weights(P['conv5.weight'][:c_out], PACK_FWD)
     out = K.conv_forward(t4, wp, mp, c_out, 1, gate=True, bias=P['conv5.bias'], scale=P['gamma'].view(-1), res=y)
+    if not keep:
+        return out, None
     saved = (x, xn, mu1, rs1, t1, g, pooled, s, y, yn, mu2, rs2, t4, c_out)
     return out, saved
 
@@ -394,16 +419,16 @@ def naf_bwd(dout, P, saved):
     return dx, G
 
 
-def naf_seq_fwd(x, P, pre, n, c_out_last=None, local=None):
-    """local = (k1, k2): TLSC inference (naf_fwd_local), nothing saved"""
+def naf_seq_fwd(x, P, pre, n, c_out_last=None, local=None, keep=True):
+    """local = (k1, k2): TLSC inference (naf_fwd_local), nothing saved.  keep=False: (x, None), as naf_fwd"""
     saved = []
     for i in range(n):
         if local is not None:
             x = naf_fwd_local(x, _sub(P, f'{pre}{i}.'), *local)
             continue
-        x, sv = naf_fwd(x, _sub(P, f'{pre}{i}.'), c_out_last if i == n - 1 else None)
+        x, sv = naf_fwd(x, _sub(P, f'{pre}{i}.'), c_out_last if i == n - 1 else None, keep=keep)
         saved.append(sv)
-    return x, saved
+    return x, (saved if keep else None)
 
 
 def naf_fwd_local(x, P, k1, k2):
@@ -548,9 +573,11 @@ def _p16_level(Cc, n_blocks):
     return P16_ON and n_blocks > 0 and fmt is not None and K.p16_supported(Cc) and Cc >= min_c
 
 
-def encoder_fwd(x, P, pre, ext_n_blocks, levels=5):
+def encoder_fwd(x, P, pre, ext_n_blocks, levels=5, keep=True, deep_only=False):
     """returns ([f1..f_levels], saved).  levels=4: the Restormer-ref file's own 4-level Encoder
-    (network_restormer_guided_arch.py:99-133)."""
+    (network_restormer_guided_arch.py:99-133).
+    keep=False: the same launches, no block operands kept -> (feats, None); with deep_only (the lq pyramid, which the match reads at
+    its deepest level alone) the shallower entries of feats are None and each level is released once the next one's conv_L has read it."""
     feats, saved = [], []
     cnt = _enc_counts(ext_n_blocks)
     for lvl in range(levels):
@@ -578,7 +605,8 @@ def encoder_fwd(x, P, pre, ext_n_blocks, levels=5):
                 _, h16 = K.conv3x3_p16(x16, wp1, mp1, Cc, bias=P[bp + 'conv1.bias'], relu=True, want32=False, want16=True)
                 o32, o16 = K.conv3x3_p16(h16, wp2, mp2, Cc, bias=P[bp + 'conv2.bias'], res=x16 if tri else x32,
                                          want32=last or not tri, want16=not last)
-                blocks.append((x16, h16))
+                if keep:
+                    blocks.append((x16, h16))
                 x16, x32 = o16, o32
             x = x32
         else:
@@ -586,11 +614,13 @@ def encoder_fwd(x, P, pre, ext_n_blocks, levels=5):
                 bp = f'{pre}blk_L{k}.{i}.'
                 h = conv_fwd(x, P[bp + 'conv1.weight'], P[bp + 'conv1.bias'], 1, 1, relu=True)
                 o = conv_fwd(h, P[bp + 'conv2.weight'], P[bp + 'conv2.bias'], 1, 1, res=x)
-                blocks.append((x, h))
+                if keep:
+                    blocks.append((x, h))
                 x = o
-        feats.append(x)
-        saved.append((xin, a, blocks))
-    return feats, saved
+        feats.append(x if not deep_only or lvl == levels - 1 else None)
+        if keep:
+            saved.append((xin, a, blocks))
+    return feats, (saved if keep else None)
 
 
 def encoder_bwd(dfeats, P, pre, ext_n_blocks, saved, G):
@@ -687,7 +717,9 @@ class Pyramids:
     __slots__ = ('N', 'stacked', 'inp_p', 'geo', 'feats', 'sv_enc', 'lq_deep', 'ref_feats', 'levels')
 
 
-def pyramids_fwd(P, cfg, inp, ref, padder_log2, levels):
+def pyramids_fwd(P, cfg, inp, ref, padder_log2, levels, keep=True):
+    """keep=False: what masa_fwd reads and nothing else -- py.lq_deep, py.ref_feats (a list masa_fwd empties level by level) and
+    py.inp_p; py.feats / py.sv_enc are None.  Stacked, a level of the lq pyramid shares its tensor with the ref level and leaves with it."""
     N, Ci, H0, W0 = inp.shape
     mult = (2 ** padder_log2) * cfg['lr_block_size']
     Hp, Wp = -(-H0 // mult) * mult, -(-W0 // mult) * mult
@@ -705,7 +737,7 @@ def pyramids_fwd(P, cfg, inp, ref, padder_log2, levels):
         _pad_into(inp.contiguous(), both[:N])
         _pad_into(ref.contiguous(), both[N:])
         py.inp_p = both[:N]
-        py.feats, py.sv_enc = encoder_fwd(both, P, 'masa_enc.', cfg['ext_n_blocks'], levels=levels)
+        py.feats, py.sv_enc = encoder_fwd(both, P, 'masa_enc.', cfg['ext_n_blocks'], levels=levels, keep=keep)
         py.lq_deep = py.feats[levels - 1][:N]
         py.ref_feats = [f[N:] for f in py.feats]
     else:
@@ -713,10 +745,12 @@ def pyramids_fwd(P, cfg, inp, ref, padder_log2, levels):
         ref_p = torch.empty(N, Ci, Hrp, Wrp, dtype=torch.float32, device=inp.device)
         _pad_into(inp.contiguous(), py.inp_p)
         _pad_into(ref.contiguous(), ref_p)
-        fl, svl = encoder_fwd(py.inp_p, P, 'masa_enc.', cfg['ext_n_blocks'], levels=levels)
-        fr, svr = encoder_fwd(ref_p, P, 'masa_enc.', cfg['ext_n_blocks'], levels=levels)
+        fl, svl = encoder_fwd(py.inp_p, P, 'masa_enc.', cfg['ext_n_blocks'], levels=levels, keep=keep, deep_only=not keep)
+        fr, svr = encoder_fwd(ref_p, P, 'masa_enc.', cfg['ext_n_blocks'], levels=levels, keep=keep)
         py.feats, py.sv_enc = (fl, fr), (svl, svr)
         py.lq_deep, py.ref_feats = fl[levels - 1], fr
+    if not keep:
+        py.feats = py.sv_enc = None
     return py, (H0, W0, Hp, Wp)
 
 
@@ -740,10 +774,12 @@ def pyramids_bwd(dwarp, py, P, cfg, sv_masa, G):
         G[k] = K.add_(g.contiguous().view(1, -1), Gl[k].contiguous().view(1, -1)).view(g.shape) if k in Gl else g
 
 
-def masa_fwd(lq4, ref_feats, N, geo, outs=None):
+def masa_fwd(lq4, ref_feats, N, geo, outs=None, keep=True):
     """lq4: deepest lq feature map [N,C,H,W]; ref_feats: the ref pyramid (finest first; 5 levels for NAFNet-ref, 4 for
     Restormer-ref), each [N,C_l,Hr_l,Wr_l].  Returns (warp list finest->coarsest like the reference's warp_ref_l,
-    saved).  outs: optional per-level destination views (the second half of the fusion blocks' concat buffers)."""
+    saved).  outs: optional per-level destination views (the second half of the fusion blocks' concat buffers).
+    keep=False: (warp, None); the search operands go as the search ends, and ref_feats -- the caller's LIST -- is emptied level by
+    level as the transfer kernel that reads a level is enqueued (its entries become None)."""
     P, Kk, side = geo.P, geo.K, geo.side
     L = len(ref_feats)
     ref4 = ref_feats[L - 1]
@@ -764,6 +800,8 @@ def masa_fwd(lq4, ref_feats, N, geo, outs=None):
         K.patch_inv_norm(lrb, 1, 1, dil=d, off=cc - d, out=invq[di])
         K.patch_inv_norm(ref4, Hr, Wr, dil=d, pad=d, out=invk[di])
     index, y1, x1 = K.coarse_argmax_box(dots, invq, invk, N, P, Hr, Wr, geo.dia_x)
+    if not keep:
+        dots = invq = invk = wp = None
     # ---- fine search (:495-513) inside the matched ref block
     refb = K.gather_ref_block(ref4, y1, x1, P, side, 1)                   # [N*P, C, side, side]
     wp, mp, per_b = K.pack_patches(lrb, 1, Kk, Kk, 1, 1, 0)
@@ -772,12 +810,18 @@ def masa_fwd(lq4, ref_feats, N, geo, outs=None):
     finvq = K.patch_inv_norm(lrb, Kk, Kk)                                 # [N*P, K, K]
     finvk = K.patch_inv_norm(refb, R1, R1)
     index_all, soft_att = K.fine_argmax(fdots, finvq, finvk, N * P, Kk * Kk, R1 * R1)
+    if not keep:
+        lq4 = ref4 = lrb = refb = wp = fdots = finvq = finvk = None
     # ---- transfer at every scale, reading the ref features directly
     warp = []
     for lvl in range(L):
         s = 2 ** (L - 1 - lvl)
         warp.append(K.transfer_fwd(ref_feats[lvl], y1, x1, index_all, soft_att, geo.py, geo.px, Kk, side, s,
                                    out=None if outs is None else outs[lvl]))
+        if not keep:
+            ref_feats[lvl] = None
+    if not keep:
+        return warp, None
     saved = (lrb, refb, finvq, finvk, index, y1, x1, index_all, soft_att)
     return warp, saved
 
@@ -836,7 +880,7 @@ def _level(cfg, l):
     return f'encoders.{l}.', cfg['enc_blk_nums'][l], f'masa_blk_enc.{l}.'
 
 
-def walk_fwd(P, cfg, inp, ref=None, seq=naf_seq_fwd, local=None):
+def walk_fwd(P, cfg, inp, ref=None, seq=naf_seq_fwd, local=None, keep=True):
     """inp [N,3,H,W] -> (out [N,3,H,W], saved): zero pad -> intro -> encoders / downs -> middle -> ups (+ skip) / decoders ->
     ending + inp -> crop.  cfg: constructor kwargs.
     ref [N,3,Hr,Wr]: guided -- MASA pyramids and match (pyramids_fwd / masa_fwd), padding to the MASA block grid, and at every level
@@ -845,19 +889,27 @@ def walk_fwd(P, cfg, inp, ref=None, seq=naf_seq_fwd, local=None):
     seq(x, P, prefix, n) -> (x, saved): the block sequence of a stage (`encoders.{l}.`, `middle_blks.`, `decoders.{l}.`)
     local: per-level TLSC pooling kernels (tlsc_kernel_sizes), handed to seq -- `NAFNetLocal`, inference only (nothing saved)
     saved = (N, (H0, W0, Hp, Wp), geo, pyr, None, None, sv_masa, S) -- geo, sv_masa None without a reference; S holds the rest by
-    name.  restormer_engine.walk_fwd saves the same prefix."""
+    name.  restormer_engine.walk_fwd saves the same prefix.
+    keep=False: a forward pass no backward follows (inference, validation) -> (out, None), the same launches with the forward-only
+    NAFBlock chains (naf_fwd); seq is called with keep=False.  Live at any moment: the concat buffers of the levels still to come (with
+    their warped reference features), the skips of the levels passed, and one block's working set -- the pyramids go when the transfer
+    has read them, a concat buffer when its level's first fusion block has, a skip when its decoder level has."""
     n_enc = len(cfg['enc_blk_nums'])
     N, _, H0, W0 = inp.shape
     chan = P['intro.weight'].shape[0]
     cats = sv_masa = None
+    kw = {} if keep else {'keep': False}
     if ref is not None:
-        pyr, sizes = pyramids_fwd(P, cfg, inp, ref, n_enc, n_enc + 1)
+        pyr, sizes = pyramids_fwd(P, cfg, inp, ref, n_enc, n_enc + 1, **kw)
         Hp, Wp = sizes[2:]
         # cat([x, warp], 1) of every fusion level without copies: the transfer kernel writes the warped reference features
         # (nf * 2^l channels) into the second half of the level's concat buffer, the conv that produces x writes the first half
         cats = [torch.empty(N, (chan << l) + pyr.ref_feats[l].shape[1], Hp >> l, Wp >> l, dtype=torch.float32, device=inp.device)
                 for l in range(n_enc + 1)]
-        _, sv_masa = masa_fwd(pyr.lq_deep, pyr.ref_feats, N, pyr.geo, outs=[c[:, chan << l:] for l, c in enumerate(cats)])
+        warp, sv_masa = masa_fwd(pyr.lq_deep, pyr.ref_feats, N, pyr.geo, outs=[c[:, chan << l:] for l, c in enumerate(cats)], **kw)
+        warp = None                                        # (views of cats)
+        if not keep:
+            pyr.lq_deep = pyr.ref_feats = None
     else:
         mult = 1 << n_enc
         Hp, Wp = -(-H0 // mult) * mult, -(-W0 // mult) * mult
@@ -865,27 +917,42 @@ def walk_fwd(P, cfg, inp, ref=None, seq=naf_seq_fwd, local=None):
         pyr = types.SimpleNamespace(inp_p=inp.contiguous() if (Hp, Wp) == (H0, W0) else K.pad_crop(inp.contiguous(), Hp, Wp), geo=None)
 
     def stage(x, pre, n, l):
-        return seq(x, P, pre, n) if local is None else seq(x, P, pre, n, local=local[l])
-    S = types.SimpleNamespace(levels=[], dec=[])
+        return seq(x, P, pre, n, **kw) if local is None else seq(x, P, pre, n, local=local[l], **kw)
+    S = types.SimpleNamespace(levels=[], dec=[]) if keep else None        # what walk_bwd reads, by name
+    skips = []
     x = conv_fwd(pyr.inp_p, P['intro.weight'], P['intro.bias'], 1, 1, out=cats[0][:, :chan] if cats else None)
     for l in range(n_enc + 1):
         pre, n, fus = _level(cfg, l)
         sv_f = None
         if cats:
-            x, sv_f = naf_seq_fwd(cats[l], P, fus, cfg['reffusion_n_blocks'][l], c_out_last=chan << l)
+            x = None                                       # (a view of cats[l])
+            x, sv_f = naf_seq_fwd(cats[l] if keep else _take(cats, l), P, fus, cfg['reffusion_n_blocks'][l], c_out_last=chan << l, **kw)
         x, sv_e = stage(x, pre, n, l)
-        S.levels.append((sv_f, sv_e, x))                   # x: the skip, and what downs.{l} reads
+        skips.append(x if l < n_enc else None)
+        if keep:
+            S.levels.append((sv_f, sv_e, x))               # x: the skip, and what downs.{l} reads
         if l < n_enc:
             x = conv_fwd(x, P[f'downs.{l}.weight'], P[f'downs.{l}.bias'], 2, 0, out=cats[l + 1][:, :chan << (l + 1)] if cats else None)
     for l in range(len(cfg['dec_blk_nums'])):
         xin = x
-        x = up_fwd(xin, P[f'ups.{l}.0.weight'], S.levels[n_enc - 1 - l][2])
+        x = up_fwd(xin, P[f'ups.{l}.0.weight'], skips[n_enc - 1 - l] if keep else _take(skips, n_enc - 1 - l))
+        if not keep:
+            xin = None
         x, sv_d = stage(x, f'decoders.{l}.', cfg['dec_blk_nums'][l], n_enc - 1 - l)
-        S.dec.append((xin, sv_d))
-    S.xe = x
+        if keep:
+            S.dec.append((xin, sv_d))
     out_p = conv_fwd(x, P['ending.weight'], P['ending.bias'], 1, 1, res=pyr.inp_p)
     out = out_p if (Hp, Wp) == (H0, W0) else K.pad_crop(out_p, H0, W0)
+    if not keep:
+        return out, None
+    S.xe = x
     return out, (N, sizes, pyr.geo, pyr, None, None, sv_masa, S)
+
+
+def _take(lst, i):
+    """lst[i], the list's reference to it given up: the callee's is then the last one"""
+    t, lst[i] = lst[i], None
+    return t
 
 
 def walk_bwd(dout, P, cfg, saved, G=None, seq=naf_seq_bwd):
@@ -938,9 +1005,9 @@ def walk_bwd(dout, P, cfg, saved, G=None, seq=naf_seq_bwd):
     return dinp, G
 
 
-def net_fwd(P, cfg, inp, ref):
-    """NAFNetRefFusion: inp, ref [N,3,H,W] -> (out [N,3,H,W], saved)"""
-    return walk_fwd(P, cfg, inp, ref)
+def net_fwd(P, cfg, inp, ref, keep=True):
+    """NAFNetRefFusion: inp, ref [N,3,H,W] -> (out [N,3,H,W], saved); keep=False: (out, None), nothing kept for a backward pass"""
+    return walk_fwd(P, cfg, inp, ref, keep=keep)
 
 
 def net_bwd(dout, P, cfg, saved, G=None):
@@ -948,9 +1015,9 @@ def net_bwd(dout, P, cfg, saved, G=None):
     return walk_bwd(dout, P, cfg, saved, G)[1]
 
 
-def unet_fwd(P, cfg, inp, local=None):
-    """`NAFNet.forward`; local: `NAFNetLocal` (TLSC inference)"""
-    return walk_fwd(P, cfg, inp, local=local)
+def unet_fwd(P, cfg, inp, local=None, keep=True):
+    """`NAFNet.forward`; local: `NAFNetLocal` (TLSC inference); keep=False: (out, None), nothing kept for a backward pass"""
+    return walk_fwd(P, cfg, inp, local=local, keep=keep)
 
 
 def unet_bwd(dout, P, cfg, saved, G=None):

@@ -881,6 +881,21 @@ def naf_tail_supported(c, hw, c_out=None):
     return ok_out and MATH in ('hx2', 'bx3') and bool(_lib.load().tdr_naf_tail_supported(int(c), int(hw)))
 
 
+def _naf_tail_desc(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out):
+    """descriptor of tdr_naf_tail_fwd / tdr_naf_tail_infer without the saved tensors (NULL: what the forward-only chain wants)"""
+    N, Cc, H, W = g.shape
+    d = _lib.TdrNafTailDesc()
+    d.N, d.C, d.HW, d.eps, d.c_out = N, Cc, H * W, float(eps), c_out
+    assert w3p.fmt == w4p.fmt == w5p.fmt
+    d.w_fmt = w3p.fmt
+    d.g, d.g_ns, d.sca, d.x, d.x_ns = g.data_ptr(), _dense_nchw(g), s.data_ptr(), x.data_ptr(), _dense_nchw(x)
+    d.w3, d.w4, d.w5 = w3p.data_ptr(), w4p.data_ptr(), w5p.data_ptr()
+    d.b3, d.beta, d.lnw, d.lnb = b3.data_ptr(), beta.data_ptr(), lnw.data_ptr(), lnb.data_ptr()
+    d.b4, d.b5, d.gamma = b4.data_ptr(), b5.data_ptr(), gamma.data_ptr()
+    d.out, d.out_ns = out.data_ptr(), _dense_nchw(out)
+    return d
+
+
 def naf_tail_fwd(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out=None):
     """fused conv3 -> +residual -> norm2 -> conv4 -> SimpleGate -> conv5 -> +residual (csrc/tdr_nafblock.hip).
     Returns (out, y, mu2, rs2, yn, t4): exactly the tensors the unfused sequence saves for the backward pass."""
@@ -894,16 +909,9 @@ def naf_tail_fwd(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma,
     t4 = torch.empty(N, 2 * Cc, H, W, dtype=torch.float32, device=dev)
     mu = torch.empty(N, H * W, dtype=torch.float32, device=dev)
     rs = torch.empty_like(mu)
-    d = _lib.TdrNafTailDesc()
-    d.N, d.C, d.HW, d.eps, d.c_out = N, Cc, H * W, float(eps), c_out
-    assert w3p.fmt == w4p.fmt == w5p.fmt
-    d.w_fmt = w3p.fmt
-    d.g, d.g_ns, d.sca, d.x, d.x_ns = g.data_ptr(), _dense_nchw(g), s.data_ptr(), x.data_ptr(), _dense_nchw(x)
-    d.w3, d.w4, d.w5 = w3p.data_ptr(), w4p.data_ptr(), w5p.data_ptr()
-    d.b3, d.beta, d.lnw, d.lnb = b3.data_ptr(), beta.data_ptr(), lnw.data_ptr(), lnb.data_ptr()
-    d.b4, d.b5, d.gamma = b4.data_ptr(), b5.data_ptr(), gamma.data_ptr()
+    d = _naf_tail_desc(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out)
     d.y, d.y_ns, d.mu, d.rs, d.yn, d.yn_ns = y.data_ptr(), _dense_nchw(y), mu.data_ptr(), rs.data_ptr(), yn.data_ptr(), _dense_nchw(yn)
-    d.t4, d.t4_ns, d.out, d.out_ns = t4.data_ptr(), _dense_nchw(t4), out.data_ptr(), _dense_nchw(out)
+    d.t4, d.t4_ns = t4.data_ptr(), _dense_nchw(t4)
     if _survey is not None:
         _survey.probe(g, 'fwd')
     check(lib.tdr_naf_tail_fwd(C.byref(d), _stream()), 'tdr_naf_tail_fwd')
@@ -911,6 +919,17 @@ def naf_tail_fwd(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma,
         _survey.probe(yn, 'fwd')
         _survey.probe(t4, 'fwd')
     return out, y, mu, rs, yn, t4
+
+
+def naf_tail_infer(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out=None):
+    """the chain of naf_tail_fwd for a pass that keeps nothing: -> out alone, bit-identical to naf_tail_fwd's (same kernel body, the
+    stores of y / yn / t4 / mu / rs compiled out)"""
+    N, Cc, H, W = g.shape
+    c_out = Cc if c_out is None else c_out
+    out = torch.empty(N, c_out, H, W, dtype=torch.float32, device=g.device)
+    d = _naf_tail_desc(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out)
+    check(_lib.load().tdr_naf_tail_infer(C.byref(d), _stream()), 'tdr_naf_tail_infer')
+    return out
 
 
 def _ln_partials_finish(ws, nparts, Cc):
@@ -990,6 +1009,18 @@ def naf_head_fwd(x, lnw, lnb, eps, w1p, b1):
         _survey.probe(x, 'fwd')
     check(lib.tdr_naf_head_fwd(C.byref(d), _stream()), 'tdr_naf_head_fwd')
     return xn, mu, rs, t1
+
+
+def naf_head_infer(x, lnw, lnb, eps, w1p, b1):
+    """norm1 -> conv1 for a pass that keeps nothing: -> t1 alone, bit-identical to naf_head_fwd's (xn, mu, rs are not written)"""
+    N, Cc, H, W = x.shape
+    t1 = torch.empty(N, 2 * Cc, H, W, dtype=torch.float32, device=x.device)
+    d = _lib.TdrNafHeadFwdDesc()
+    d.N, d.C, d.HW, d.w_fmt = N, Cc, H * W, w1p.fmt
+    d.x, d.x_ns, d.lnw, d.lnb, d.eps = x.data_ptr(), _dense_nchw(x), lnw.data_ptr(), lnb.data_ptr(), float(eps)
+    d.w1, d.b1, d.t1, d.t1_ns = w1p.data_ptr(), b1.data_ptr(), t1.data_ptr(), _dense_nchw(t1)
+    check(_lib.load().tdr_naf_head_infer(C.byref(d), _stream()), 'tdr_naf_head_infer')
+    return t1
 
 
 def naf_head_bwd(dt1, x, mu, rs, lnw, w1tp, res, defer_finish=False):

@@ -95,6 +95,25 @@ class _UNetFn(torch.autograd.Function):
         return (dinp, None, None) + tuple(G[k] for k in ctx.names)
 
 
+def _infer_fwd(what, fwd, names, params, cfg, *images):
+    """the forward pass when no gradient can be asked of its result -- grad mode is off (`torch.no_grad()`, as in torch; `.eval()`
+    alone does not select it), or neither an image nor a parameter requires grad: engine.net_fwd / unet_fwd with keep=False, outside
+    autograd -> the output alone (bit-identical to the autograd node's), or None when a gradient may be asked.
+    The weights are packed afresh from the parameters as they are now, outside any kernels.PackPlan: a validation pass between two
+    optimiser steps must neither read a training step's cached packs nor record its own weights into that step's plan."""
+    if torch.is_grad_enabled() and (any(t.requires_grad for t in images) or any(p.requires_grad for p in params)):
+        return None
+    from ... import kernels as K
+    require_gpu(images[0], what)
+    P = dict(zip(names, [p.detach() for p in params]))
+    prev = K.set_pack_plan(None)
+    try:
+        with torch.no_grad():
+            return fwd(P, cfg, *[t.detach() for t in images], keep=False)[0]
+    finally:
+        K.set_pack_plan(prev)
+
+
 def make_layer(block, n_layers):
     return nn.Sequential(*[block() for _ in range(n_layers)])
 
@@ -220,7 +239,8 @@ class NAFNet(_NAFBase):
 
     def forward(self, inp):
         names, params = _named(self)
-        return _UNetFn.apply(inp, names, self.cfg, *params)
+        out = _infer_fwd('NAFNet', E.unet_fwd, names, params, self.cfg, inp)
+        return out if out is not None else _UNetFn.apply(inp, names, self.cfg, *params)
 
 
 class NAFNetRefFusion(_NAFBase):
@@ -255,7 +275,8 @@ class NAFNetRefFusion(_NAFBase):
 
     def forward(self, inp, ref):
         names, params = _named(self)
-        return _NetFn.apply(inp, ref, names, self.cfg, *params)
+        out = _infer_fwd('NAFNetRefFusion', E.net_fwd, names, params, self.cfg, inp, ref)
+        return out if out is not None else _NetFn.apply(inp, ref, names, self.cfg, *params)
 
 
 class NAFNetLocal(NAFNet):
