@@ -7,7 +7,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from textualdegremoval_amd import engine as E, kernels as K  # noqa: E402
+from textualdegremoval_amd import engine as E, kernels as K, leaves as L  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
 from test_hip_nafblock_fused import block_params, rnd  # noqa: E402
@@ -33,13 +33,13 @@ def bwd(saved, leaves):
     d = dout
     G = {}
     if leaves == 'late':
-        with E.deferred_join(), E.late_leaves(G):
+        with L.deferred_join(), E.late_leaves(G):
             for i in reversed(range(NB)):
-                E.set_late_prefix(f'b{i}.')
+                L.set_prefix(f'b{i}.')
                 d, g = E.naf_bwd(d, Ps[i], saved[i])
-            E.run_late_leaves(G, lambda: None)
+            L.run_late_leaves(G, lambda: None)
     else:
-        with E.deferred_join():
+        with L.deferred_join():
             for P, sv in zip(reversed(Ps), reversed(saved)):
                 d, g = E.naf_bwd(d, P, sv)
     return d
@@ -71,10 +71,10 @@ _, saved = fwd()
 for rep in range(2):
     t_full, keep1 = timed(lambda: bwd(saved, 'side'))
     t_late, keep2 = timed(lambda: bwd(saved, 'late'))
-    orig = E._leaf_wgrad1x1
-    E._leaf_wgrad1x1 = lambda *a, **k: None
+    orig = L.leaf_wgrad1x1
+    L.leaf_wgrad1x1 = lambda *a, **k: None
     t_nolf, keep3 = timed(lambda: bwd(saved, 'side'))
-    E._leaf_wgrad1x1 = orig
+    L.leaf_wgrad1x1 = orig
     print(f'per block: forward {t_f:.1f} us; backward with leaves on the side stream {t_full:.1f}, leaves deferred + grouped '
           f'{t_late:.1f}, without the conv1/4/5 weight gradients {t_nolf:.1f} us', flush=True)
     del keep1, keep2, keep3

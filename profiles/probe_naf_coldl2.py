@@ -7,7 +7,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from textualdegremoval_amd import engine as E, kernels as K  # noqa: E402
+from textualdegremoval_amd import engine as E, kernels as K, leaves as L  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
 from test_hip_nafblock_fused import block_params, rnd  # noqa: E402
@@ -24,7 +24,7 @@ def chain(Ps):
         h, sv = E.naf_fwd(h, P)
         saved.append(sv)
     d = dout
-    with E.deferred_join():
+    with L.deferred_join():
         for P, sv in zip(reversed(Ps), reversed(saved)):
             d, G = E.naf_bwd(d, P, sv)
     return h, d

@@ -221,7 +221,7 @@ def test_deferred_leaf_weight_gradients_match(E):
     and run on a second stream beside the MASA-encoder backward -- same kernels on the same operands, so every tensor outside the
     MASA encoder (atomics in the transfer backward) is bit-identical to the single-stream backward; the set of keys is the same and
     the deferred operands were still alive (a recycled buffer would show up as a wrong gradient)."""
-    from textualdegremoval_amd import kernels as K
+    from textualdegremoval_amd import kernels as K, leaves as L
     cfg = O.default_cfg(width=8, nf=8, ext_n_blocks=[1, 1, 1, 1], reffusion_n_blocks=[1, 1, 1, 1, 1])
     P = cuda_params(O.synth_params(cfg, seed=2))
     lq, gt, ref = O.synth_pair(2, 128, 128, seed=12)
@@ -240,7 +240,7 @@ def test_deferred_leaf_weight_gradients_match(E):
         finally:
             E.DEFER_WGRAD = prev
             E.GROUP_LEAVES = grp
-    assert E._late is None
+    assert L.current is None
     for other in res[1:]:
         assert set(res[0]) == set(other)
         for k in res[0]:

@@ -19,6 +19,7 @@ import torch
 
 from . import engine as E
 from . import kernels as K
+from . import leaves as L
 from . import restormer_engine as R
 
 
@@ -146,7 +147,7 @@ def tblock_bwd(dout, P, heads, ln_type, saved):
     dy = R._ln_bwd(dyn, y, mu2, rs2, P, 'norm2.', ln_type, G, add=dout)
     dxn = attn_bwd(dy, P, heads, sv_a, G)
     dx = R._ln_bwd(dxn, x, mu1, rs1, P, 'norm1.', ln_type, G, add=dy)
-    E.maybe_join()
+    L.maybe_join()
     return dx, G
 
 
@@ -270,5 +271,5 @@ def mefc_bwd(dout, P, pre, saved, G):
     dlg = K.softmax_rows(wts, dy=dwts).view(N, STEPS * nops)
     dh1, G[pre + 'layers.0.ca_fc.2.weight'], G[pre + 'layers.0.ca_fc.2.bias'] = K.linear_small_bwd(dlg, None, h1, P[pre + 'layers.0.ca_fc.2.weight'])
     demb, G[pre + 'layers.0.ca_fc.0.weight'], G[pre + 'layers.0.ca_fc.0.bias'] = K.linear_small_bwd(dh1, h1, emb, P[pre + 'layers.0.ca_fc.0.weight'])
-    E.maybe_join()
+    L.maybe_join()
     return K.plane_add_(dx, demb, 1.0 / (H * W))

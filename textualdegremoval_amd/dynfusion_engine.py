@@ -16,6 +16,7 @@ import torch
 
 from . import engine as E
 from . import kernels as K
+from . import leaves as L
 from .kernels import PACK_DGRAD_S1, PACK_FWD
 
 KV_DIM = 10 * 1024          # in_features of every projection (`nn.Linear(10 * 1024, ., bias=False)`, :257, :305)
@@ -210,7 +211,7 @@ def dyn_unet_bwd(dout, P, cfg, saved, need_dkv=True, G=None):
     """-> (dinp, dkv or None, G, dK): gradients w.r.t. the image, k_v (shape [N, 10240]), every parameter, and the projection outputs"""
     kvf, Kt, tab = saved[-3:]
     dK = torch.empty_like(Kt)            # every column is written by exactly one block's reductions
-    with E.deferred_join():              # (the walk's side branch is joined after the projection launches)
+    with L.deferred_join():              # (the walk's side branch is joined after the projection launches)
         dinp, G = E.walk_bwd(dout, P, cfg, saved, G,
                              seq=lambda d, P, pre, n, sv, G: _seq_bwd(d, P, pre + 'layers.', n, sv, Kt, dK, G))
         dkv = proj_bwd(tab, kvf, dK, G, need_dkv)

@@ -9,6 +9,10 @@ call into libtdr_hip.so (torch only allocates and views memory).
 The U-Net itself is walked by ONE pair, walk_fwd / walk_bwd: NAFNetRefFusion (net_fwd / net_bwd: a reference image, MASA
 pyramids and fusion blocks), NAFNet / NAFNetLocal (unet_fwd / unet_bwd) and NAFNetDynamicFusion (dynfusion_engine, its own
 block sequence) are callers that differ by arguments.
+
+Parameter gradients nothing downstream reads are issued as leaves of the deferred-leaf scheduler (leaves.py: which launches wait, which
+share a launch, on which stream they run); its switches (DEFER_WGRAD, GROUP_LEAVES, ...) are attributes of this module, read by
+late_leaves() when a whole-network backward is entered.
 """
 import contextlib
 import os
@@ -17,6 +21,7 @@ import types
 import torch
 
 from . import kernels as K
+from . import leaves as L
 from .kernels import (EPI_GATEBWD, EPI_PSHUF, PACK_DGRAD_2X2S2, PACK_DGRAD_3X3S2, PACK_DGRAD_S1, PACK_FWD)
 
 LN_EPS = 1e-6
@@ -40,37 +45,15 @@ def _put(G, pre, g):
         G[pre + k] = v
 
 
-# Weight gradients run on the side stream (kernels.on_side).  A backward helper called on its own joins the side
-# branch before it returns (its results are then ordinary current-stream tensors); inside a whole-network backward
-# the joins are deferred to the end so the weight-gradient branch overlaps the data-gradient chain of later layers.
-_defer_join = 0
-
-
-class deferred_join:
-    def __enter__(self):
-        global _defer_join
-        _defer_join += 1
-        return self
-
-    def __exit__(self, *exc):
-        global _defer_join
-        _defer_join -= 1
-        if _defer_join == 0:
-            K.side_join()
-        return False
-
-
-def maybe_join():
-    if _defer_join == 0:
-        K.side_join()
-
-
-# Leaf weight gradients of the NAFBlocks (conv1 / conv4 / conv5: nothing downstream in the backward reads them) can be DEFERRED to the
-# end of the main backward chain and run on a second HIP stream next to the MASA-encoder backward (kernels.lane): at bs 4 the 1x1 weight
-# gradients of the deep levels are L2 / HBM-bound launches of 512 small workgroups, the encoder's 3x3 data / weight gradients are matrix-
-# bound launches of 256 - 2048 large ones -- complementary resources, where the NAFBlock chain itself (135 KB of LDS per workgroup) leaves
-# no room for a second kernel.  The operands stay referenced until the join (288 GB of HBM: ~14 GB of gradient operands kept alive).
-# Only without a gradient exchange: with collectives the buckets are cut in arrival order inside the backward (parallel.GradAllReducer).
+# The deferred-leaf schedule (leaves.py): leaf weight gradients of the NAFBlocks (conv1 / conv4 / conv5: nothing downstream in the backward
+# reads them) can be DEFERRED to the end of the main backward chain and run on a second HIP stream next to the MASA-encoder backward
+# (kernels.lane): at bs 4 the 1x1 weight gradients of the deep levels are L2 / HBM-bound launches of 512 small workgroups, the encoder's
+# 3x3 data / weight gradients are matrix-bound launches of 256 - 2048 large ones -- complementary resources, where the NAFBlock chain itself
+# (135 KB of LDS per workgroup) leaves no room for a second kernel.  The operands stay referenced until the join (288 GB of HBM: ~14 GB of
+# gradient operands kept alive).  Only without a gradient exchange: with collectives the buckets are cut in arrival order inside the backward
+# (parallel.GradAllReducer).
+# The switches live here (module switches -- tests, probes and bench.py set them before a backward starts); late_leaves() reads them when a
+# pass is entered and hands them to the leaves.Pass.
 DEFER_WGRAD = True
 DEFER_LN_FINISH = True                                                  # also the reductions of the LayerNorm-gradient partials
 # deferred 1x1 leaf weight gradients of one shape (a level's conv1 / conv4, its conv5) share ONE launch + ONE reduction
@@ -83,181 +66,21 @@ GROUP_LEAVES = True
 BATCH_FINISH = True
 # data-parallel runs: the leaves of a level queued and run (grouped) at the level's end instead of one launch per leaf inside the chain
 LEVEL_LEAVES = True
-_level_mode = False
 FORCE_DP_SCHEDULE = os.environ.get('TDR_FORCE_DP_SCHEDULE', '0') == '1'    # measurement aid: schedule the leaves as a data-parallel run would, on one GPU
 SERIAL_LEAVES = False    # measurement aid (bench.py's roofline leg): the deferred leaves on the CURRENT stream, before the main chain
-_late = None            # [(prefix, closure -> {name: grad})] while a whole-network backward collects deferred leaves
-_late_pre = ''
+DEBUG_LEAVES = False     # check at run time that no operand of a queued leaf was written in place (the RULE in leaves.py)
 
 
-# RULE for queued leaves: a leaf reads its operands (`keep`, and whatever its closure names) when run_late_leaves() runs it -- after
-# the whole main backward chain.  Nothing may write those tensors in place (K.add_ and friends) or rebind the closure's names between
-# queueing and the run; every operand must be listed in `keep`.  engine.DEBUG_LEAVES = True checks the tensors' version counters at run time.
-DEBUG_LEAVES = False        # (module switch)
-
-
-def _leaf(keep, fn, G):
-    """run a parameter-gradient leaf now (optionally on the side stream), or queue it for the deferred pass"""
-    if _late is not None:
-        if DEBUG_LEAVES:
-            stamp = [(t, t._version) for t in keep if torch.is_tensor(t)]
-            inner = fn
-
-            def fn():
-                for t, v in stamp:
-                    assert t._version == v, 'a queued weight-gradient operand was modified in place before its deferred leaf ran'
-                return inner()
-        _late.append((_late_pre, fn, keep))
-        return
-    with K.on_side(*keep):
-        for k, v in fn().items():
-            G[k] = v                    # (item by item: a GradSink collector acts on __setitem__)
-
-
-def _leaf_fin(names, fin, G):
-    """a leaf that reduces per-workgroup partials: fin() -> the gradients of `names`.  Finishers that carry a `batch` description
-    (kernels._ln_partials_finish, kernels.dwsg_bwd) are queued as requests, so that _run_leaves can run all of one shape as one launch"""
-    b = getattr(fin, 'batch', None)
-    if _late is not None and BATCH_FINISH and b is not None:
-        _late.append((_late_pre, ('fin', b[0], b, names, fin), (b[1],)))
-        return
-    _leaf((), lambda: dict(zip(names, fin())), G)
-
-
-def _leaf_wgrad1x1(keep, req, post, G, want_db=True):
-    """a leaf whose work is ONE 1x1 weight gradient (with the bias gradient unless want_db=False) -- req = (x, dout, Cout, Cin, gate) --
-    followed by `post(g, db) -> {name: grad}` (db None without a bias): queued for the grouped launch when leaves are being collected and
-    the shape qualifies, an ordinary leaf otherwise"""
-    x, dout, Cout, Cin, gate = req
-    if _late is not None and GROUP_LEAVES:
-        key = K.wgrad1x1_group_key(x, dout, Cout, Cin, gate)
-        if key is not None:
-            if DEBUG_LEAVES:        # the same in-place check _leaf() installs, for the operands of a grouped request
-                stamp = [(t, t._version) for t in keep if torch.is_tensor(t)]
-                inner_post = post
-
-                def post(g, db):
-                    for t, v in stamp:
-                        assert t._version == v, 'a queued weight-gradient operand was modified in place before its grouped leaf ran'
-                    return inner_post(g, db)
-            _late.append((_late_pre, ('grp', key + (want_db,), req + (want_db,), post), keep))
-            return
-
-    def run():
-        r = K.conv_wgrad(x, dout, Cout, Cin, 1, gate=gate, want_db=want_db)
-        return post(*K.side_keep(*r)) if want_db else post(K.side_keep(r), None)
-    _leaf(keep, run, G)
-
-
-class late_leaves:
-    """`with late_leaves(G):` around a whole-network backward: leaves are queued (when allowed) until run_late_leaves().
+def late_leaves(G, level_ok=False):
+    """`with late_leaves(G):` around a whole-network backward: leaves are queued (when allowed) until L.run_late_leaves().
     With a gradient exchange (G.reducer.collective) nothing is deferred to the end -- the buckets are cut in arrival order inside the
-    backward -- but a caller that marks its level boundaries (level_ok=True + level_end(G) after each level) still gets the leaves of
+    backward -- but a caller that marks its level boundaries (level_ok=True + L.level_end(G) after each level) still gets the leaves of
     a LEVEL queued and run together at its end, on the current stream: the 1x1 weight gradients of the level as grouped launches."""
+    coll = bool(getattr(getattr(G, 'reducer', None), 'collective', False)) or FORCE_DP_SCHEDULE
+    level = coll and level_ok and LEVEL_LEAVES
+    return L.collecting(DEFER_WGRAD and (not coll or level), level=level, group=GROUP_LEAVES, batch_finish=BATCH_FINISH,
+                        serial=SERIAL_LEAVES, debug=DEBUG_LEAVES)
 
-    def __init__(self, G, level_ok=False):
-        coll = bool(getattr(getattr(G, 'reducer', None), 'collective', False)) or FORCE_DP_SCHEDULE
-        self.level = coll and level_ok and LEVEL_LEAVES
-        self.on = DEFER_WGRAD and not K.SIDE_WGRAD and (not coll or self.level)
-
-    def __enter__(self):
-        global _late, _grp_seq, _level_mode
-        _late = [] if self.on else None
-        _level_mode = self.on and self.level
-        _grp_seq = 0
-        return self
-
-    def __exit__(self, *exc):
-        global _late, _level_mode
-        _late = None
-        _level_mode = False
-        return False
-
-
-def level_end(G):
-    """level boundary of a backward pass that exchanges gradients: run what the level queued (grouped), hand its gradients over now"""
-    global _late
-    if not _level_mode or not _late:
-        return
-    late, _late = _late, []
-    for pre, g in _run_leaves(late, serial=True):
-        _put(G, pre, g)
-    late.clear()
-
-
-def set_late_prefix(pre):
-    global _late_pre
-    _late_pre = pre
-
-
-_grp_seq = 0            # grouped launches issued so far in this pass (the call-site index of their pinned pointer tables)
-
-
-def _run_leaves(late, serial=False):
-    """the queued leaves on lane 0 (the current stream if serial / SERIAL_LEAVES), 1x1 requests of one shape grouped -> [(prefix, grads)].
-    Queue entries: a closure -> {name: grad}; ('grp', key, request, post) -- a 1x1 weight gradient, post(g, db) -> {..}; ('fin', key, batch,
-    names, fin) -- a finishing reduction (_leaf_fin)"""
-    global _grp_seq
-    import contextlib
-    ctx = contextlib.nullcontext() if (SERIAL_LEAVES or serial) else K.lane(0, sync=True)
-    with ctx:
-        groups, fins, outs = {}, {}, {}
-        for i, (pre, fn, _) in enumerate(late):
-            if isinstance(fn, tuple):
-                (fins if fn[0] == 'fin' else groups).setdefault(fn[1], []).append(i)
-        scp = []                                                 # posts that are a scaled_conv_param_grads call on a group's result
-        for key, idxs in groups.items():                         # one launch + one reduction per shape
-            res = K.wgrad1x1_group([late[i][1][2][:5] for i in idxs], seq=_grp_seq, want_db=key[-1])
-            _grp_seq += 1
-            for i, r in zip(idxs, res):
-                if BATCH_FINISH and getattr(late[i][1][3], 'scp', None) is not None:
-                    scp.append((i, r))                           # (conv5 / gamma: naf_bwd's post5.scp) -- one launch for all of them below
-                else:
-                    outs[i] = late[i][1][3](*r)
-        if len(scp) > 1:
-            items = []
-            for i, (g5, s5) in scp:
-                w5, b5, gam, c_out, c, _fmt = late[i][1][3].scp
-                items.append((g5.view(c_out, c), s5, w5, b5, gam))
-            for (i, _r), r3 in zip(scp, K.scaled_conv_param_grads_multi(items, seq=_grp_seq)):
-                outs[i] = late[i][1][3].scp[5](*K.side_keep(*r3))
-            _grp_seq += 1
-        else:
-            for i, r in scp:
-                outs[i] = late[i][1][3](*r)
-        for kind, idxs in fins.items():                          # finishing reductions: one table-driven launch per kind (shapes in the table)
-            if len(idxs) == 1:
-                i = idxs[0]
-                outs[i] = dict(zip(late[i][1][3], late[i][1][4]()))
-                continue
-            multi = K.pair_sum_partials_multi if kind == 'ln' else K.dw_param_finish_multi
-            for i, r in zip(idxs, multi([late[i][1][2][1:] for i in idxs], seq=_grp_seq)):
-                outs[i] = dict(zip(late[i][1][3], r))
-            _grp_seq += 1
-        return [(pre, outs[i] if isinstance(fn, tuple) else fn()) for i, (pre, fn, _) in enumerate(late)]
-
-
-def run_late_leaves(G, main_chain):
-    """deferred leaves on lane 0, `main_chain()` on the current stream, join, then hand the gradients to the collector in order"""
-    global _late, _grp_seq
-    if _level_mode:                 # gradient exchange: the remainder of the last level, then the main chain -- nothing runs beside it
-        level_end(G)
-        _late = None
-        _grp_seq = 0
-        main_chain()
-        return
-    late, _late = _late, None
-    if not late:
-        _grp_seq = 0
-        main_chain()
-        return
-    results = _run_leaves(late)
-    _grp_seq = 0
-    main_chain()
-    K.lanes_join()
-    for pre, g in results:
-        _put(G, pre, g)
-    late.clear()      # (operands referenced until here: the allocator cannot recycle them under a running lane kernel)
 
 
 # ---------------------------------------------------------------------------
@@ -335,7 +158,7 @@ def naf_bwd(dout, P, saved):
     dev = x.device
     G = {}
     beta, gamma = P['beta'].view(-1), P['gamma'].view(-1)
-    late = _late is not None and DEFER_LN_FINISH
+    late = L.current is not None and DEFER_LN_FINISH
     # ---- conv5 / gamma chain (parameter gradients only: a leaf off the data-gradient chain)
     def fmt5(dw5, db5, dgam):
         g = {}
@@ -353,8 +176,7 @@ def naf_bwd(dout, P, saved):
 
     def post5(G5, S5):
         return fmt5(*K.side_keep(*K.scaled_conv_param_grads(G5.view(c_out, c), S5, P['conv5.weight'], P['conv5.bias'], gamma)))
-    post5.scp = (P['conv5.weight'], P['conv5.bias'], gamma, c_out, c, fmt5)      # (what _run_leaves needs to batch it with its level's others)
-    _leaf_wgrad1x1((t4, dout), (t4, dout, c_out, c, True), post5, G)
+    L.leaf_wgrad1x1((t4, dout), (t4, dout, c_out, c, True), post5, G, scp=(P['conv5.weight'], P['conv5.bias'], gamma, c_out, c, fmt5))
     fused = FUSE_TAIL and K.naf_tail_supported(c, H * W, c_out) and dout.is_contiguous() and \
         _dgrad_fused_ok()
     if fused:
@@ -367,15 +189,15 @@ def naf_bwd(dout, P, saved):
         else:
             dy, dt4, gw2, gb2 = K.naf_tail_bwd(dout, gamma, t4, y, mu2, rs2, P['norm2.weight'], w5t, w4t, defer_finish=late)
         if late:        # the reduction of the per-workgroup LayerNorm-gradient partials is a leaf too (gw2: closure over its private buffer)
-            _leaf_fin(('norm2.weight', 'norm2.bias'), gw2, G)
+            L.leaf_fin(('norm2.weight', 'norm2.bias'), gw2, G)
         else:
             G['norm2.weight'], G['norm2.bias'] = gw2, gb2
     else:
         wp, mp, *_ = K.pack_weights(P['conv5.weight'][:c_out], PACK_DGRAD_S1)
         dt4 = K.conv_forward(dout, wp, mp, c, 1, epi=EPI_GATEBWD, kscale=gamma, aux=t4)
     # ---- conv4
-    _leaf_wgrad1x1((yn, dt4), (yn, dt4, 2 * c, c, False),
-                   lambda g4, b4: {'conv4.weight': g4.view(2 * c, c, 1, 1), 'conv4.bias': b4}, G)
+    L.leaf_wgrad1x1((yn, dt4), (yn, dt4, 2 * c, c, False),
+                    lambda g4, b4: {'conv4.weight': g4.view(2 * c, c, 1, 1), 'conv4.bias': b4}, G)
     if not fused:
         wp, mp, *_ = K.pack_weights(P['conv4.weight'], PACK_DGRAD_S1)
         dyn = K.conv_forward(dt4, wp, mp, c, 1)
@@ -396,26 +218,26 @@ def naf_bwd(dout, P, saved):
         wp, mp, *_ = K.pack_weights(P['conv3.weight'], PACK_DGRAD_S1)
         dg = K.conv_forward(dy, wp, mp, c, 1, kscale=beta, scale=s, bias2=dpooled, bias2_mul=1.0 / (H * W))
         dt1, gdw, gdb = K.dwsg_bwd(dg, t1, P['conv2.weight'], P['conv2.bias'], defer_finish=late)
-    if callable(gdw):       # the finish of the depthwise parameter gradients: one more leaf
-        _leaf_fin(('conv2.weight', 'conv2.bias'), gdw, G)
+    if isinstance(gdw, K.Finisher):       # the finish of the depthwise parameter gradients: one more leaf
+        L.leaf_fin(('conv2.weight', 'conv2.bias'), gdw, G)
     else:
         G['conv2.weight'], G['conv2.bias'] = gdw, gdb
     # ---- conv1
-    _leaf_wgrad1x1((xn, dt1), (xn, dt1, 2 * c, c, False),
-                   lambda g1, b1: {'conv1.weight': g1.view(2 * c, c, 1, 1), 'conv1.bias': b1}, G)
+    L.leaf_wgrad1x1((xn, dt1), (xn, dt1, 2 * c, c, False),
+                    lambda g1, b1: {'conv1.weight': g1.view(2 * c, c, 1, 1), 'conv1.bias': b1}, G)
     if FUSE_TAIL and K.naf_tail_supported(c, H * W) and _dgrad_fused_ok() and x.is_contiguous() and dy.is_contiguous():
         # conv1 dgrad -> norm1 bwd (+ dy) in one launch
         w1t = K.pack_weights(P['conv1.weight'], PACK_DGRAD_S1)[0]
         dx, gw1, gb1 = K.naf_head_bwd(dt1, x, mu1, rs1, P['norm1.weight'], w1t, dy, defer_finish=late)
         if late:
-            _leaf_fin(('norm1.weight', 'norm1.bias'), gw1, G)
+            L.leaf_fin(('norm1.weight', 'norm1.bias'), gw1, G)
         else:
             G['norm1.weight'], G['norm1.bias'] = gw1, gb1
     else:
         wp, mp, *_ = K.pack_weights(P['conv1.weight'], PACK_DGRAD_S1)
         dxn = K.conv_forward(dt1, wp, mp, c, 1)
         dx, G['norm1.weight'], G['norm1.bias'] = K.layernorm2d_bwd(dxn, x, mu1, rs1, P['norm1.weight'], add=dy)
-    maybe_join()
+    L.maybe_join()
     return dx, G
 
 
@@ -459,12 +281,11 @@ def naf_fwd_local(x, P, k1, k2):
 
 
 def naf_seq_bwd(dout, P, pre, n, saved, G):
-    global _late_pre
     for i in reversed(range(n)):
-        _late_pre = f'{pre}{i}.'
+        L.set_prefix(f'{pre}{i}.')
         dout, g = naf_bwd(dout, _sub(P, f'{pre}{i}.'), saved[i])
         _put(G, f'{pre}{i}.', g)
-    _late_pre = ''
+    L.set_prefix('')
     return dout
 
 
@@ -480,7 +301,7 @@ def conv_fwd(x, w, b, stride, pad, res=None, relu=False, out=None):
 
 def conv_bwd(dout, x, w, stride, pad, need_dx=True, add_to_dx=None, bias=True, into=None):
     """returns (dx or None, dw, db); db is None for a bias-free conv (bias=False).
-    into = (G, weight name, bias name or None): the parameter gradients go to the collector instead -- as a leaf (_leaf: deferred to
+    into = (G, weight name, bias name or None): the parameter gradients go to the collector instead -- as a leaf (leaves.leaf: deferred to
     the second stream when a whole-network backward collects leaves) -- and (dx, None, None) is returned."""
     Cout, Cin, KH, _ = w.shape
 
@@ -493,12 +314,12 @@ def conv_bwd(dout, x, w, stride, pad, need_dx=True, add_to_dx=None, bias=True, i
     dw = db = None
     if into is not None:
         Gc, wname, bname = into
-        set_late_prefix('')
+        L.set_prefix('')             # (named in full)
 
         def leaf_named():
             gw, gb = leaf()
             return {wname: gw} if (gb is None or bname is None) else {wname: gw, bname: gb}
-        _leaf((x, dout), leaf_named, Gc)
+        L.leaf((x, dout), leaf_named, Gc)
     else:
         with K.on_side(x, dout):
             dw, db = leaf()
@@ -516,7 +337,7 @@ def conv_bwd(dout, x, w, stride, pad, need_dx=True, add_to_dx=None, bias=True, i
             dx = K.conv_forward(dout, wp, mp, 4 * Cin, 2, pad=0, OH=OH, OW=OW, epi=EPI_PSHUF, res=add_to_dx)
         else:
             raise NotImplementedError(f'conv dgrad KH={KH} stride={stride} pad={pad}')
-    maybe_join()
+    L.maybe_join()
     return dx, dw, db
 
 
@@ -533,14 +354,14 @@ def up_bwd(dout, x, w, into=None):
     dT = K.pixel_unshuffle2(dout)
     dw = None
     if into is not None:
-        set_late_prefix('')
-        _leaf((x, dT), lambda: {into[1]: K.conv_wgrad(x, dT, C2, Cc, 1).view(C2, Cc, 1, 1)}, into[0])
+        L.set_prefix('')
+        L.leaf((x, dT), lambda: {into[1]: K.conv_wgrad(x, dT, C2, Cc, 1).view(C2, Cc, 1, 1)}, into[0])
     else:
         with K.on_side(x, dT):
             dw = K.conv_wgrad(x, dT, C2, Cc, 1).view(C2, Cc, 1, 1)
     wp, mp, *_ = K.pack_weights(w, PACK_DGRAD_S1)
     dx = K.conv_forward(dT, wp, mp, Cc, 1)
-    maybe_join()
+    L.maybe_join()
     return dx, dw
 
 
@@ -627,9 +448,9 @@ def encoder_bwd(dfeats, P, pre, ext_n_blocks, saved, G):
     """dfeats: list of per-level grads (or None).  Input-image gradient is not needed."""
     cnt = _enc_counts(ext_n_blocks)
     dnext = None                      # gradient flowing from level lvl+1 into feats[lvl]
-    with deferred_join():
+    with L.deferred_join():
         _encoder_bwd_levels(dfeats, P, pre, cnt, saved, G, dnext)
-    maybe_join()
+    L.maybe_join()
     return None
 
 
@@ -684,7 +505,7 @@ def _encoder_bwd_levels(dfeats, P, pre, cnt, saved, G, dnext):
         # the feature gradient of the level below joins in the data-gradient epilogue instead of a separate add
         dnext, G[f'{pre}conv_L{k}.weight'], G[f'{pre}conv_L{k}.bias'] = conv_bwd(
             dpre, xin, w, 1 if lvl == 0 else 2, 1, need_dx=(lvl > 0), add_to_dx=dfeats[lvl - 1] if lvl > 0 else None)
-    maybe_join()
+    L.maybe_join()
     return None
 
 
@@ -961,15 +782,15 @@ def walk_bwd(dout, P, cfg, saved, G=None, seq=naf_seq_bwd):
     `G` may be a caller's dict-like collector (e.g. parallel.GradSink, which starts the RCCL all-reduce of a gradient bucket as
     soon as its last tensor is stored): the order of the stores is behaviour.
     seq(d, P, prefix, n, saved, G) -> d: the backward of walk_fwd's seq.
-    Guided: leaf weight gradients are queued (late_leaves; per level with a gradient exchange, level_end) and run next to the MASA
-    backward at the end (run_late_leaves).  Un-guided: they run at once -- grouped 1x1 weight gradients are not bit-identical to
+    Guided: leaf weight gradients are queued (late_leaves; per level with a gradient exchange, leaves.level_end) and run next to the MASA
+    backward at the end (leaves.run_late_leaves).  Un-guided: they run at once -- grouped 1x1 weight gradients are not bit-identical to
     ungrouped ones (see restormer_engine.net_bwd)."""
     G = {} if G is None else G
     N, (H0, W0, Hp, Wp), _, pyr, _, _, sv_masa, S = saved[:8]
     guided = sv_masa is not None
     n_enc = len(cfg['enc_blk_nums'])
     chan = P['intro.weight'].shape[0]
-    with deferred_join(), (late_leaves(G, level_ok=True) if guided else contextlib.nullcontext()):
+    with L.deferred_join(), (late_leaves(G, level_ok=True) if guided else contextlib.nullcontext()):
         dout = dout.contiguous()
         if (Hp, Wp) != (H0, W0):
             dout = K.pad_crop(dout, Hp, Wp)
@@ -979,7 +800,7 @@ def walk_bwd(dout, P, cfg, saved, G=None, seq=naf_seq_bwd):
         for l in reversed(range(len(cfg['dec_blk_nums']))):
             xin, sv_d = S.dec[l]
             d = seq(d, P, f'decoders.{l}.', cfg['dec_blk_nums'][l], sv_d, G)
-            level_end(G)
+            L.level_end(G)
             dskips[n_enc - 1 - l] = d                      # gradient of `x + enc_skip` w.r.t. the skip
             d, _ = up_bwd(d, xin, P[f'ups.{l}.0.weight'], into=(G, f'ups.{l}.0.weight'))
         dwarp = [None] * (n_enc + 1)
@@ -993,7 +814,7 @@ def walk_bwd(dout, P, cfg, saved, G=None, seq=naf_seq_bwd):
             d = seq(d, P, pre, n, sv_e, G)
             if guided:
                 dcat = naf_seq_bwd(d, P, fus, cfg['reffusion_n_blocks'][l], sv_f, G)
-                level_end(G)
+                L.level_end(G)
                 dwarp[l] = dcat[:, chan << l:]
                 d = dcat[:, :chan << l]                    # batch-strided view: every consumer takes an image stride
         dinp, _, _ = conv_bwd(d, pyr.inp_p, P['intro.weight'], 1, 1, need_dx=not guided, add_to_dx=None if guided else dout,
@@ -1001,7 +822,7 @@ def walk_bwd(dout, P, cfg, saved, G=None, seq=naf_seq_bwd):
         if dinp is not None and (Hp, Wp) != (H0, W0):
             dinp = K.pad_crop(dinp, H0, W0)
         if guided:
-            run_late_leaves(G, lambda: pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G))
+            L.run_late_leaves(G, lambda: pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G))
     return dinp, G
 
 

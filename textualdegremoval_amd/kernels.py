@@ -844,11 +844,24 @@ def dwsg_fwd(t, w, b):
     return g, pooled
 
 
+class Finisher:
+    """what a backward launch with defer_finish=True returns in place of its parameter gradients: calling it reduces the per-workgroup
+    partials the launch left in `ws` (a buffer of their own) -> the gradients.  kind 'ln' (dims = (nparts, C)) / 'dw' (dims = (N, C, H, W)):
+    pair_sum_partials_multi / dw_param_finish_multi do the same for several (ws, *dims) in one launch; None: only the call itself"""
+    __slots__ = ('kind', 'ws', 'dims', '_run')
+
+    def __init__(self, kind, ws, dims, run):
+        self.kind, self.ws, self.dims, self._run = kind, ws, dims, run
+
+    def __call__(self):
+        return self._run()
+
+
 def dwsg_bwd(dg, t, w, b, dg_bias=None, dg_bias_mul=1.0, defer_finish=False):
     """dg_bias [N, C]: per-plane constant added to dg (times dg_bias_mul) as it is read -- the pooled gradient of the SCA
     branch when the conv3 data gradient comes out of the fused tail kernel without it.
-    defer_finish (one-pass backward only; otherwise ignored): returns (dt, fin, None), fin() -> (dw, db) reduces the per-workgroup
-    partials of the parameter gradients, which then live in a buffer of their own."""
+    defer_finish (one-pass backward only; otherwise ignored): returns (dt, fin, None), the Finisher fin() -> (dw, db) reduces the
+    per-workgroup partials of the parameter gradients, which then live in a buffer of their own."""
     lib = _lib.load()
     N, C2, H, W = t.shape
     Cc = C2 // 2
@@ -865,8 +878,7 @@ def dwsg_bwd(dg, t, w, b, dg_bias=None, dg_bias_mul=1.0, defer_finish=False):
             db = torch.empty(C2, dtype=torch.float32, device=dev)
             check(lib.tdr_dw_param_finish(ws.data_ptr(), N, Cc, H, W, dw.data_ptr(), db.data_ptr(), _stream()), 'tdr_dw_param_finish')
             return dw, db
-        fin.batch = ('dw', ws, N, Cc, H, W)
-        return dt, fin, None
+        return dt, Finisher('dw', ws, (N, Cc, H, W), fin), None
     dw = torch.empty(C2, 1, 3, 3, dtype=torch.float32, device=dev)
     db = torch.empty(C2, dtype=torch.float32, device=dev)
     ws = workspace(lib.tdr_dwsg_ws_floats(N, Cc, H, W), dev)
@@ -933,23 +945,22 @@ def naf_tail_infer(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamm
 
 
 def _ln_partials_finish(ws, nparts, Cc):
-    """closure that reduces the per-workgroup LayerNorm-gradient partials a fused NAFBlock backward left in its PRIVATE `ws`"""
+    """Finisher that reduces the per-workgroup LayerNorm-gradient partials a fused NAFBlock backward left in its PRIVATE `ws`"""
     def fin():
         gw = torch.empty(Cc, dtype=torch.float32, device=ws.device)
         gb = torch.empty_like(gw)
         check(_lib.load().tdr_pair_sum_partials(ws.data_ptr(), nparts, Cc, gw.data_ptr(), gb.data_ptr(),
                                                 ws.data_ptr() + 4 * nparts * 2 * Cc, _stream()), 'tdr_pair_sum_partials')
         return gw, gb
-    if nparts <= 1024:                       # (the one-stage reduction: what pair_sum_partials_multi batches)
-        fin.batch = ('ln', ws, nparts, Cc)
-    return fin
+    # (nparts <= 1024: the one-stage reduction, what pair_sum_partials_multi batches)
+    return Finisher('ln' if nparts <= 1024 else None, ws, (nparts, Cc), fin)
 
 
 def naf_tail_bwd(dout, gamma, t4, y, mu, rs, lnw, w5tp, w4tp, w3tp=None, beta=None, sca=None, defer_finish=False):
     """fused conv5 dgrad -> SimpleGate bwd -> conv4 dgrad -> norm2 bwd (+ skip) (csrc/tdr_nafblock.hip).
     Returns (dy, dt4, gw2, gb2[, dgp]); with w3tp / beta / sca the conv3 data gradient dgp = sca * W3^T (beta * dy) comes out
     of the same launch (without the pooled-gradient term: dwsg_bwd(dg_bias=...) adds it).
-    defer_finish: gw2 is a closure -> (gw2, gb2) and gb2 is None -- the reduction of the per-workgroup partials (a leaf) is left to
+    defer_finish: gw2 is a Finisher -> (gw2, gb2) and gb2 is None -- the reduction of the per-workgroup partials (a leaf) is left to
     the caller, the partials live in a buffer of their own."""
     lib = _lib.load()
     N, Cc, H, W = y.shape

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from ... import dynfusion_engine as D
-from ... import engine as E
+from ... import leaves as L
 from .nafnet_arch_utils import LayerNorm2d, require_gpu
 from .network_nafnet_guided_arch import NAFBlock, NAFNet, NAFNetLocal, SimpleGate, _named  # noqa: F401
 
@@ -55,7 +55,7 @@ class _DynBlockFn(torch.autograd.Function):
     def backward(ctx, dout):
         tab, kvf, Kt = ctx.proj
         dK = torch.empty_like(Kt)
-        with E.deferred_join():
+        with L.deferred_join():
             dx, G = D.dyn_naf_bwd(dout.contiguous(), ctx.P, ctx.saved, Kt, dK)
             dkv = D.proj_bwd(tab, kvf, dK, G, ctx.needs_input_grad[1])
         ctx.saved = ctx.proj = None

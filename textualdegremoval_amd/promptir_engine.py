@@ -11,6 +11,7 @@ engine (no gradient, as in the reference where their .grad stays None).
 """
 from . import engine as E
 from . import kernels as K
+from . import leaves as L
 from . import restormer_engine as R
 
 # ---------------------------------------------------------------------------
@@ -57,9 +58,9 @@ def _prompt_stage_fwd(x, P, cfg, k):
 def _prompt_stage_bwd(d, P, cfg, k, saved, G):
     c, sv_p, sv_t, t = saved
     d = R._pw_bwd(d, t, P, f'reduce_noise_level{k}', G)
-    E.set_late_prefix(f'noise_level{k}.')
+    L.set_prefix(f'noise_level{k}.')
     dcat, g = R.tblock_bwd(d, E._sub(P, f'noise_level{k}.'), cfg['heads'][2], cfg['LayerNorm_type'], sv_t)
-    E.set_late_prefix('')
+    L.set_prefix('')
     E._put(G, f'noise_level{k}.', g)
     dx = K.slice_channels(dcat, 0, c)
     demb, inv = prompt_bwd(K.slice_channels(dcat, c, dcat.shape[1]), P, f'prompt{k}.', sv_p, G)

@@ -27,6 +27,7 @@ import torch
 
 from . import engine as E
 from . import kernels as K
+from . import leaves as L
 from .kernels import EPI_PSHUF, PACK_DGRAD_S1, PACK_FWD
 
 LN_EPS = 1e-5        # :190,208
@@ -63,10 +64,10 @@ def _pw_bwd(dout, x, P, name, G):
     w = P[name + '.weight']
     Cout, Cin = w.shape[0], w.shape[1]
     has_b = (name + '.bias') in P
-    # parameter gradient: a leaf off the data-gradient chain (engine._leaf_wgrad1x1: deferred, leaves of one shape in one grouped launch)
+    # parameter gradient: a leaf off the data-gradient chain (leaves.leaf_wgrad1x1: deferred, leaves of one shape in one grouped launch)
     def post(g, db):
         return {name + '.weight': g.view(Cout, Cin, 1, 1), name + '.bias': db} if has_b else {name + '.weight': g.view(Cout, Cin, 1, 1)}
-    E._leaf_wgrad1x1((x, dout), (x, dout, Cout, Cin, False), post, G, want_db=has_b)
+    L.leaf_wgrad1x1((x, dout), (x, dout, Cout, Cin, False), post, G, want_db=has_b)
     wp, mp, *_ = K.pack_weights(w, PACK_DGRAD_S1)
     return K.conv_forward(dout, wp, mp, Cin, 1)
 
@@ -128,7 +129,7 @@ def tblock_bwd(dout, P, heads, ln_type, saved):
         G['attn.qkv_dwconv.bias'] = db
     dxn = _pw_bwd(dt, xn, P, 'attn.qkv', G)
     dx = _ln_bwd(dxn, x, mu1, rs1, P, 'norm1.', ln_type, G, add=dy)
-    E.maybe_join()
+    L.maybe_join()
     return dx, G
 
 
@@ -143,11 +144,11 @@ def fblock_bwd(dout, P, heads, ln_type, saved, tblock=tblock_bwd):
     sv, z = saved
     dalpha = K.dot(dout, z)
     dz = K.axpby_dev(dout, P['alpha'])
-    with E.deferred_join():
+    with L.deferred_join():
         dx, G = tblock(dz, P, heads, ln_type, sv)
     G['alpha'] = dalpha
     dx = K.add_(dx, dout)
-    E.maybe_join()
+    L.maybe_join()
     return dx, G
 
 
@@ -162,11 +163,11 @@ def seq_fwd(x, P, pre, n, heads, ln_type, tblock=tblock_fwd, fusion=False):
 
 def seq_bwd(d, P, pre, n, heads, ln_type, saved, G, tblock=tblock_bwd, fusion=False):
     for i in reversed(range(n)):
-        E.set_late_prefix(f'{pre}{i}.')
+        L.set_prefix(f'{pre}{i}.')
         Pi = E._sub(P, f'{pre}{i}.')
         d, g = fblock_bwd(d, Pi, heads, ln_type, saved[i], tblock) if fusion else tblock(d, Pi, heads, ln_type, saved[i])
         E._put(G, f'{pre}{i}.', g)
-    E.set_late_prefix('')              # (top-level leaves -- reduce_chan_level*, skip_conv -- carry full names)
+    L.set_prefix('')                   # (top-level leaves -- reduce_chan_level*, skip_conv -- carry full names)
     return d
 
 
@@ -283,9 +284,9 @@ def walk_fwd(P, cfg, inp, ref, size_msg, tblock=tblock_fwd, fuse=range(4), head=
 def walk_bwd(dout, P, cfg, saved, G=None, tblock=tblock_bwd, head=None, pre_up=None, tail=None, dual_pixel=False, late=True):
     """-> G, the parameter gradients of walk_fwd (the input image is data).  The stages are the backward of the ones passed to
     walk_fwd: head(d, P, cfg, saved, G), pre_up(d, P, cfg, l, saved, G), tail(d, P, cfg, saved, G) -> gradient of the stage input.
-    late: leaf weight gradients queued (E.late_leaves) and run next to the MASA backward at the end (E.run_late_leaves)."""
+    late: leaf weight gradients queued (engine.late_leaves) and run next to the MASA backward at the end (leaves.run_late_leaves)."""
     G = {} if G is None else G
-    with E.deferred_join(), (E.late_leaves(G) if late else contextlib.nullcontext()):
+    with L.deferred_join(), (E.late_leaves(G) if late else contextlib.nullcontext()):
         N, (H0, W0, Hp, Wp), _, pyr, _, _, sv_masa, S = saved
         hd, ln, nb, nfz = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg.get('reffusion_n_blocks')
         dout = dout.contiguous()
@@ -328,7 +329,7 @@ def walk_bwd(dout, P, cfg, saved, G=None, tblock=tblock_bwd, head=None, pre_up=N
             d = head(d, P, cfg, S.head, G)
         _conv_bwd(d, pyr.inp_p, P, 'patch_embed.proj', G, need_dx=False)
         if late:
-            E.run_late_leaves(G, lambda: E.pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G) if sv_masa is not None else None)
+            L.run_late_leaves(G, lambda: E.pyramids_bwd(dwarp, pyr, P, cfg, sv_masa, G) if sv_masa is not None else None)
     return G
 
 

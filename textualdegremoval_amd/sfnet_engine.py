@@ -11,6 +11,7 @@ import torch
 
 from . import engine as E
 from . import kernels as K
+from . import leaves as L
 from .kernels import EPI_PSHUF, PACK_FWD
 
 BASE = 32
@@ -232,7 +233,7 @@ def net_bwd(douts, P, saved, G=None):
      sv_c1, sv_d2, sv_f5) = saved
     G = {} if G is None else G
     d4, d2, d1 = (t.contiguous() for t in douts)
-    with E.deferred_join():
+    with L.deferred_join():
         d = conv_bwd(d1, P, 'feat_extract.5.', sv_f5, G)
         d = blocks_bwd(d, P, 'Decoder.2.', num_res, sv_d2, G)
         dz, dres1 = cat_conv_bwd(d, P, 'Convs.1.', sv_c1, G)
@@ -253,5 +254,5 @@ def net_bwd(douts, P, saved, G=None):
         conv_bwd(d, P, 'feat_extract.0.', sv_f0, G, need_dx=False)
         scm_bwd(dz4, P, 'SCM1.', sv_scm1, G)
         scm_bwd(dz2, P, 'SCM2.', sv_scm2, G)
-    E.maybe_join()
+    L.maybe_join()
     return G
