@@ -22,9 +22,9 @@ extern "C" {
 
 /* C-ABI version: bumped with every incompatible change of this header (100 rounds 1-2, 101 round 3, 102 round 4, 103 - 104
  * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
- * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*); the
+ * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*); the
  * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
-#define TDR_ABI_VERSION 109
+#define TDR_ABI_VERSION 110
 int tdr_version(void);
 const char* tdr_last_error(void);
 
@@ -230,6 +230,20 @@ typedef struct TdrWg1GroupEntry {
 int tdr_wgrad1x1_group_supported(const TdrWgradDesc* d);
 int64_t tdr_wgrad1x1_group_ws_floats(const TdrWgradDesc* d, int nprob);
 int tdr_wgrad1x1_group(const TdrWgradDesc* d, int nprob, const void* table, void* stream);
+
+/* Grouped 3x3 weight gradients on P16 operands (ABI 110): the weight / bias gradients of the ResidualBlock convolutions of one MASA
+ * encoder level (network_nafnet_guided_arch.py:44-59,110-143: 4 blocks x 2 convolutions) have one shape, so they share ONE launch; its
+ * workgroups each take a longer slice of one problem's pixels -- 1 / nprob of the split-K partials of tdr_wgrad3x3_p16, none at all
+ * (and no reduction launch) where one slice per problem fills the chip.  Deterministic, and a problem's bits do not depend on its row.
+ * `d` carries the common shape and format (N, Cin, Cout, H, W, fmt); its pointers are ignored.  `table`: TdrWg1GroupEntry[nprob] in
+ * DEVICE memory; entry p: in = in16, dout = dout16, part = the problem's own workspace of tdr_wgrad3x3_p16_group_ws_floats(d, nprob)
+ * floats ([nsplit][Cout][Cin][9], then [nsplit][Cout] at dbpart = part + nsplit * Cout * Cin * 9, or dbpart NULL for no bias gradient;
+ * 0 floats when nsplit == 1: g / db are written directly and part / dbpart are not read), g [Cout][Cin][3][3], db [Cout] or NULL.
+ * tdr_wgrad3x3_p16_group_plan: the slices per problem (nsplit), the (image, strip, row chunk) units of a problem's pixels and the
+ * most units one workgroup walks (any of the three pointers may be NULL). */
+int64_t tdr_wgrad3x3_p16_group_ws_floats(const TdrWgradP16Desc* d, int nprob);
+int tdr_wgrad3x3_p16_group_plan(const TdrWgradP16Desc* d, int nprob, int* nsplit, int* units, int* units_per_wg);
+int tdr_wgrad3x3_p16_group(const TdrWgradP16Desc* d, int nprob, const void* table, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Streaming (HBM-bound) kernels.

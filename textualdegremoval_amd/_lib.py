@@ -15,7 +15,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TDR_LIB_PATH', os.path.join(_HERE, 'libtdr_hip.so'))   # override: profiling probe builds
 
-ABI_VERSION = 109      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
+ABI_VERSION = 110      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
 c_fp = C.c_void_p      # device pointers travel as integers
 i32, i64, f32 = C.c_int, C.c_int64, C.c_float
 
@@ -163,6 +163,9 @@ SIGNATURES = {
     'tdr_wgrad1x1_group_supported': (i32, [C.POINTER(TdrWgradDesc)]),
     'tdr_wgrad1x1_group_ws_floats': (i64, [C.POINTER(TdrWgradDesc), i32]),
     'tdr_wgrad1x1_group': (i32, [C.POINTER(TdrWgradDesc), i32, c_fp, c_fp]),
+    'tdr_wgrad3x3_p16_group_ws_floats': (i64, [C.POINTER(TdrWgradP16Desc), i32]),
+    'tdr_wgrad3x3_p16_group_plan': (i32, [C.POINTER(TdrWgradP16Desc), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    'tdr_wgrad3x3_p16_group': (i32, [C.POINTER(TdrWgradP16Desc), i32, c_fp, c_fp]),
     'tdr_layernorm2d_fwd': (i32, [c_fp, i64, c_fp, c_fp, f32, i32, i32, i32, i32, c_fp, c_fp, c_fp, c_fp]),
     'tdr_ln_ws_floats': (i64, [i32, i32, i32]),
     'tdr_layernorm2d_bwd': (i32, [c_fp, c_fp, i64, c_fp, c_fp, c_fp, c_fp, i64, i32, i32, i32, i32, i32, c_fp, c_fp, c_fp,

@@ -57,7 +57,8 @@ def _put(G, pre, g):
 DEFER_WGRAD = True
 DEFER_LN_FINISH = True                                                  # also the reductions of the LayerNorm-gradient partials
 # deferred 1x1 leaf weight gradients of one shape (a level's conv1 / conv4, its conv5) share ONE launch + ONE reduction
-# (kernels.wgrad1x1_group, csrc/tdr_wgrad_1x1.hip): no per-launch ramp / prologue / partial write / reduction launch, 1 / 8 of the partials
+# (kernels.wgrad1x1_group, csrc/tdr_wgrad_1x1.hip): no per-launch ramp / prologue / partial write / reduction launch, 1 / 8 of the partials;
+# likewise the 3x3 weight gradients of a MASA-encoder level on plane tensors (kernels.wgrad3x3_p16_group, _encoder_bwd_levels)
 GROUP_LEAVES = True
 # ... and the small finishing reductions queued with them (LayerNorm-gradient partials, depthwise parameter partials, the conv5 / gamma
 # parameter gradients behind a grouped weight gradient) run as ONE table-driven launch per kind (kernels.*_multi; the shapes travel in the table): 112 of the 184
@@ -463,25 +464,43 @@ def _encoder_bwd_levels(dfeats, P, pre, cnt, saved, G, dnext):
             continue
         if blocks and isinstance(blocks[0][0], K.P16):
             d16, d32 = K.p16_from_f32(d, fmt=blocks[0][0].fmt), d
+            # the 2 * cnt weight gradients of the level have one shape: ONE grouped launch at the level's end (K.wgrad3x3_p16_group: 1 / 8
+            # of the split-K partials of 8 launches) -- their gradient planes stay alive until then, one level's at a time
+            fmts = {t.fmt for bl in blocks for t in bl} | {d16.fmt}
+            grouped = GROUP_LEAVES and 2 * cnt[lvl] > 1 and len(fmts) == 1
+            late = []                                                # [(parameter prefix, input planes, gradient planes)]
             for i in reversed(range(cnt[lvl])):
                 bp = f'{pre}blk_L{k}.{i}.'
                 x16, h16 = blocks[i]
                 w1, w2 = P[bp + 'conv1.weight'], P[bp + 'conv2.weight']
                 Cc = w1.shape[0]
-                with K.on_side(h16.buf, d16.buf):
-                    gw, G[bp + 'conv2.bias'] = K.wgrad3x3_p16(h16, d16, want_db=True)
-                    G[bp + 'conv2.weight'] = gw.view(Cc, Cc, 3, 3)
+                if grouped:
+                    late.append((bp + 'conv2', h16, d16))
+                else:
+                    with K.on_side(h16.buf, d16.buf):
+                        gw, G[bp + 'conv2.bias'] = K.wgrad3x3_p16(h16, d16, want_db=True)
+                        G[bp + 'conv2.weight'] = gw.view(Cc, Cc, 3, 3)
                 wp, mp, *_ = K.pack_weights(w2, PACK_DGRAD_S1)
                 _, dh16 = K.conv3x3_p16(d16, wp, mp, Cc, mask=h16, want32=False, want16=True)
-                with K.on_side(x16.buf, dh16.buf):
-                    gw, G[bp + 'conv1.bias'] = K.wgrad3x3_p16(x16, dh16, want_db=True)
-                    G[bp + 'conv1.weight'] = gw.view(Cc, Cc, 3, 3)
+                if grouped:
+                    late.append((bp + 'conv1', x16, dh16))
+                else:
+                    with K.on_side(x16.buf, dh16.buf):
+                        gw, G[bp + 'conv1.bias'] = K.wgrad3x3_p16(x16, dh16, want_db=True)
+                        G[bp + 'conv1.weight'] = gw.view(Cc, Cc, 3, 3)
                 wp, mp, *_ = K.pack_weights(w1, PACK_DGRAD_S1)
                 # the first block's input is the level's ReLU output `a`: its mask rides on this epilogue (conv + res, then mask);
                 # the gradient leaves the level as fp32 (conv_L's backward), stays a pair otherwise
                 first = i == 0
                 d32, d16 = K.conv3x3_p16(dh16, wp, mp, Cc, res=d32 if d32 is not None else d16, mask=a if first else None,
                                          want32=first, want16=not first)
+            if late:
+                with K.on_side(*[t.buf for _, x16, g16 in late for t in (x16, g16)]):
+                    res = K.wgrad3x3_p16_group([(x16, g16) for _, x16, g16 in late], seq=('enc3x3', pre, lvl), want_db=True)
+                    for (name, x16, g16), (gw, gb) in zip(late, res):
+                        G[name + '.bias'] = gb
+                        G[name + '.weight'] = gw.view(g16.C, x16.C, 3, 3)
+                late.clear()
             d = d32
         else:
             for i in reversed(range(cnt[lvl])):

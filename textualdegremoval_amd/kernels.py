@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI (include/tdr.h).  PyTorch is plumbing
 here: it owns device memory and the HIP stream; all arithmetic happens in
 libtdr_hip.so.  Every wrapper enqueues on torch's current stream."""
+import contextlib
 import ctypes as C
 import os
 
@@ -801,6 +802,51 @@ def wgrad1x1_group(reqs, seq=0, want_db=True):
             _survey.probe(do, 'grad')
     check(lib.tdr_wgrad1x1_group(C.byref(d), n, tab.data_ptr(), _stream()), 'tdr_wgrad1x1_group')
     return [(g[i].view(1, Cout, Cin, 1, 1), db[i] if want_db else None) for i in range(n)]
+
+
+def _wgrad3x3_p16_group_desc(x16, d16):
+    d = TdrWgradP16Desc()
+    d.N, d.Cin, d.H, d.W, d.Cout = x16.N, x16.C, x16.H, x16.W, d16.C
+    d.fmt = x16.fmt
+    return d
+
+
+def wgrad3x3_p16_group_plan(x16, d16, nprob):
+    """(slices per problem, units per problem, most units one workgroup walks) of a grouped launch of nprob problems of this shape"""
+    d = _wgrad3x3_p16_group_desc(x16, d16)
+    ns, un, upw = C.c_int(), C.c_int(), C.c_int()
+    check(_lib.load().tdr_wgrad3x3_p16_group_plan(C.byref(d), nprob, C.byref(ns), C.byref(un), C.byref(upw)), 'tdr_wgrad3x3_p16_group_plan')
+    return ns.value, un.value, upw.value
+
+
+def wgrad3x3_p16_group(reqs, seq, want_db=True):
+    """reqs: [(x16, d16)] P16 operands of ONE shape and plane format (the ResidualBlock convolutions of an encoder level).  One launch and
+    one fixed-order reduction (none where one slice per problem fills the chip) for all of them (csrc/tdr_wgrad_p16.hip).
+    seq: hashable name of the call site for its pinned-table pool (_grp_table) -- not an integer: those number the leaf scheduler's groups.
+    Returns [(g [1, Cout, Cin, 3, 3], db [Cout] or None)] in request order."""
+    lib = _lib.load()
+    x0, d0 = reqs[0]
+    assert all((x.N, x.C, x.H, x.W, x.fmt, do.C, do.fmt) == (x0.N, x0.C, x0.H, x0.W, x0.fmt, d0.C, x0.fmt) and (do.N, do.H, do.W) == (x.N, x.H, x.W)
+               for x, do in reqs), 'wgrad3x3_p16_group: one shape and plane format per group'
+    dev = x0.buf.device
+    n, Cin, Cout = len(reqs), x0.C, d0.C
+    d = _wgrad3x3_p16_group_desc(x0, d0)
+    per = int(lib.tdr_wgrad3x3_p16_group_ws_floats(C.byref(d), n))
+    nsplit = per // (Cout * (Cin * 9 + 1))
+    ws = workspace(per * n, dev, 'wgrad_group') if per else None
+    g = torch.empty(n, Cout, Cin, 3, 3, dtype=torch.float32, device=dev)
+    db = torch.empty(n, Cout, dtype=torch.float32, device=dev) if want_db else None
+    rows = []
+    for i, (x, do) in enumerate(reqs):
+        part = ws.data_ptr() + 4 * per * i if per else 0
+        rows += [x.data_ptr(), do.data_ptr(), part, part + 4 * nsplit * Cout * Cin * 9 if (want_db and per) else 0, g.data_ptr() + 4 * Cout * Cin * 9 * i,
+                 db.data_ptr() + 4 * Cout * i if want_db else 0]
+    # inside on_side the launch goes to the side stream: so does the upload of its table
+    with torch.cuda.stream(_side_stream) if _side_active else contextlib.nullcontext():
+        tab = _upload_table(rows, seq, dev)
+    side_keep(tab)
+    check(lib.tdr_wgrad3x3_p16_group(C.byref(d), n, tab.data_ptr(), _stream()), 'tdr_wgrad3x3_p16_group')
+    return [(g[i].view(1, Cout, Cin, 3, 3), db[i] if want_db else None) for i in range(n)]
 
 
 def layernorm2d_fwd(x, w, b, eps, center=True):
