@@ -332,6 +332,11 @@ int tdr_mdta_softmax(const float* G, const float* ss, const float* temp, int N, 
  * d[q;k] = W [q;k], and dtemp [heads].  ws >= N*heads floats. */
 int tdr_mdta_bwd(const float* G, const float* ss, const float* temp, const float* A, const float* dA, int N, int C,
                  int heads, float* W, float* dtemp, float* ws, void* stream);
+/* Forward-only: `project_out` folded into the per-image attention weights, Wo (A v) = (Wo A) v.  AT [N,Cp,Cp] as
+ * tdr_mdta_softmax / tdr_tksa_softmax write it, Wo [C,C] (project_out.weight) -> Wf [N,Cp,Cp] in the same packed layout:
+ * Wf[n][j][r] = sum_{i in head(j)} Wo[r][i] * AT[n][j][i], one fmaf chain over the c = C/heads terms in ascending i; zero outside
+ * [0,C) x [0,C) (the whole matrix is written).  wp = Wf computes Wo attn v in one 1x1 convolution.  Wf must not alias AT. */
+int tdr_attn_fold_proj(const float* AT, const float* Wo, int N, int C, int heads, float* Wf, void* stream);
 /* out = a * alpha[0] + b  (b may be NULL): TransformerResFusionBlock `x * alpha + shortcut` (:353) and its backward */
 int tdr_axpby_dev(const float* a, const float* alpha, const float* b, int64_t numel, float* out, void* stream);
 /* out[0] = sum a*b (fixed-order two-stage, double accumulation of the partials); ws >= 512 floats */

@@ -190,6 +190,7 @@ SIGNATURES = {
     'tdr_mdta_pad': (i32, [i32]),
     'tdr_mdta_softmax': (i32, [c_fp, c_fp, c_fp, i32, i32, i32, c_fp, c_fp, c_fp]),
     'tdr_mdta_bwd': (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, c_fp, c_fp, c_fp, c_fp]),
+    'tdr_attn_fold_proj': (i32, [c_fp, c_fp, i32, i32, i32, c_fp, c_fp]),
     'tdr_axpby_dev': (i32, [c_fp, c_fp, c_fp, i64, c_fp, c_fp]),
     'tdr_dot': (i32, [c_fp, c_fp, i64, c_fp, c_fp, c_fp]),
     'tdr_pixel_shuffle2': (i32, [c_fp, i32, i32, i32, i32, c_fp, c_fp]),

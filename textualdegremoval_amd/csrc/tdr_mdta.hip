@@ -13,6 +13,7 @@
 //                          packed weight matrix W [2C x 2C] per image so that  d[q;k] = W [q;k]  is a single 1x1 conv:
 //                            W[i][C+j] = W[C+j][i] = dG^_ij / (|q_i||k_j|),  W[i][i] = -rho_i/|q_i|^2,
 //                            W[C+j][C+j] = -rho'_j/|k_j|^2,  rho_i = sum_j dG^_ij G^_ij,  rho'_j = sum_i dG^_ij G^_ij
+//     tdr_attn_fold_proj   forward-only: Wf = Wo A in the same packed layout, so that attn v and project_out are one conv
 //   plus the small glue of TransformerResFusionBlock (x*alpha + shortcut, :353) and PixelShuffle (:391).
 // All reductions are fixed-order (deterministic).
 #include "tdr_common.h"
@@ -348,6 +349,60 @@ __global__ __launch_bounds__(256) void tksa_bwd_kernel(const float* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Forward-only fold of `project_out` into the per-image attention weights: Wo (A v) = (Wo A) v, so a forward pass that
+// keeps nothing for a backward needs neither the `o = A v` plane nor the second 1x1 launch.  Wf is emitted in the packed
+// layout AT has: Wf[n][j][r] = sum_{i in head(j)} Wo[r][i] * AT[n][j][i]  (A is block-diagonal over heads: c terms).
+// grid (ceil(Cp / 64), heads * chunks + pad chunks, N), chunks = ceil(c / 16): a block owns 64 columns r and 16 rows j of
+// one head -- lane = r (coalesced stores), a wave owns 4 rows.  LDS: wt [c][65] = the Wo tile transposed (Wo rows are read
+// along i, coalesced; the odd pitch keeps both the transposed write and the lane-contiguous read off bank conflicts) and
+// at [16][c] = the rows of AT (read as broadcasts).  The c terms are one fmaf chain in ascending i.  The blocks past
+// heads * chunks write the zero rows C .. Cp - 1; every block writes zeros in the columns C .. Cp - 1: the whole
+// [Cp][Cp] matrix is written, as tdr_mdta_softmax leaves AT (the per-image re-pack and the exact kernel read all of it).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int FOLD_RT = 64, FOLD_JT = 16, FOLD_PITCH = FOLD_RT + 1;
+
+__global__ __launch_bounds__(256) void attn_fold_proj_kernel(const float* __restrict__ AT, const float* __restrict__ Wo, int C, int c,
+                                                            int Cp, int heads, int chunks, float* __restrict__ Wf) {
+    extern __shared__ float lds[];
+    float* wt = lds;                        // [c][FOLD_PITCH]
+    float* at = lds + c * FOLD_PITCH;       // [FOLD_JT][c]
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, n = blockIdx.z;
+    const int r0 = blockIdx.x * FOLD_RT, r = r0 + lane;
+    float* Wfn = Wf + (long)n * Cp * Cp;
+    if ((int)blockIdx.y >= heads * chunks) {                                    // the zero rows below the matrix
+        const int j0 = C + ((int)blockIdx.y - heads * chunks) * FOLD_JT + wv * 4;
+        for (int q = 0; q < 4; ++q)
+            if (j0 + q < Cp && r < Cp) Wfn[(long)(j0 + q) * Cp + r] = 0.f;
+        return;
+    }
+    const int h = blockIdx.y / chunks, jl0 = (blockIdx.y % chunks) * FOLD_JT, hc = h * c;
+    const float* ATn = AT + (long)n * Cp * Cp;
+    for (int idx = threadIdx.x; idx < FOLD_RT * c; idx += 256) {
+        const int rr = idx / c, i = idx - rr * c;
+        wt[i * FOLD_PITCH + rr] = r0 + rr < C ? Wo[(long)(r0 + rr) * C + hc + i] : 0.f;
+    }
+    for (int idx = threadIdx.x; idx < FOLD_JT * c; idx += 256) {
+        const int jj = idx / c, i = idx - jj * c;
+        at[idx] = jl0 + jj < c ? ATn[(long)(hc + jl0 + jj) * Cp + hc + i] : 0.f;
+    }
+    __syncthreads();
+    const float* a = at + wv * 4 * c;
+    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+    for (int i = 0; i < c; ++i) {
+        const float w = wt[i * FOLD_PITCH + lane];
+        acc0 = fmaf(w, a[i], acc0);
+        acc1 = fmaf(w, a[c + i], acc1);
+        acc2 = fmaf(w, a[2 * c + i], acc2);
+        acc3 = fmaf(w, a[3 * c + i], acc3);
+    }
+    const float acc[4] = {acc0, acc1, acc2, acc3};
+    const int jl = jl0 + wv * 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (jl + q < c && r < Cp) Wfn[(long)(hc + jl + q) * Cp + r] = r < C ? acc[q] : 0.f;
+}
+
 __global__ void tksa_da_kernel(const float* __restrict__ part, int nparts, float* __restrict__ da) {
     const int q = threadIdx.x;
     if (q >= 4) return;
@@ -482,6 +537,19 @@ extern "C" int tdr_tksa_softmax(const float* G, const float* ss, const float* te
     else
         hipLaunchKernelGGL(tksa_softmax_kernel<3>, dim3(heads, N), dim3(256), 0, st, G, ss, temp, am, kk, C, C / heads, Cp, A, AT);
     TDR_LAUNCH_CHECK("tksa_softmax");
+    return TDR_OK;
+}
+
+extern "C" int tdr_attn_fold_proj(const float* AT, const float* Wo, int N, int C, int heads, float* Wf, void* stream) {
+    TDR_REQUIRE(AT && Wo && Wf, "tdr_attn_fold_proj: null pointer");
+    TDR_REQUIRE(N > 0 && N <= 65535 && heads > 0 && C % heads == 0 && C / heads <= 192,
+                "tdr_attn_fold_proj: need 0 < N <= 65535, C %% heads == 0 and C/heads <= 192 (N=%d C=%d heads=%d)", N, C, heads);
+    TDR_REQUIRE(AT != Wf, "tdr_attn_fold_proj: Wf must not alias AT");
+    const int c = C / heads, Cp = tdr_mdta_pad(C), chunks = tdr_cdiv(c, FOLD_JT);
+    const size_t lds = ((size_t)c * FOLD_PITCH + (size_t)FOLD_JT * c) * sizeof(float);        // <= 62208 bytes at c = 192
+    const dim3 grid(tdr_cdiv(Cp, FOLD_RT), heads * chunks + tdr_cdiv(Cp - C, FOLD_JT), N);
+    hipLaunchKernelGGL(attn_fold_proj_kernel, grid, dim3(256), lds, (hipStream_t)stream, AT, Wo, C, c, Cp, heads, chunks, Wf);
+    TDR_LAUNCH_CHECK("attn_fold_proj");
     return TDR_OK;
 }
 

@@ -31,18 +31,23 @@ def _am(P):
     return am
 
 
-def attn_fwd(xn, P, heads, res=None):
-    """Attention.forward (:274-328) on the normalised input; `res` is added to the projection (the block's skip)."""
+def attn_fwd(xn, P, heads, res=None, keep=True):
+    """Attention.forward (:274-328) on the normalised input; `res` is added to the projection (the block's skip).
+    keep=False: (y, None); t goes after the depthwise conv, and the tail is restormer_engine.attn_tail_fwd's (project_out folded into
+    the per-image weights)"""
     N, Cc, H, W = xn.shape
     t = R._pw_fwd(xn, P, 'attn.qkv')
+    if not keep:
+        xn = None
     qkv = K.dwconv_fwd(t, P['attn.qkv_dwconv.weight'], P.get('attn.qkv_dwconv.bias'))
+    if not keep:
+        t = None
     ss = K.row_sumsq(qkv, 2 * Cc)
     Gm = K.conv_wgrad(qkv[:, Cc:2 * Cc], qkv[:, :Cc], Cc, Cc, 1, per_image=True, fp16_range=True).view(N, Cc, Cc)
     am = _am(P)
     A, AT = K.tksa_softmax(Gm, ss, P['attn.temperature'], am, heads)
-    o = R._img_conv(qkv[:, 2 * Cc:], AT, Cc)
-    y = R._pw_fwd(o, P, 'attn.project_out', res=res)
-    return y, (xn, t, qkv, ss, Gm, am, A, o)
+    y, o = R.attn_tail_fwd(qkv[:, 2 * Cc:], AT, P, heads, res, keep)
+    return y, ((xn, t, qkv, ss, Gm, am, A, o) if keep else None)
 
 
 def attn_bwd(dy, P, heads, saved, G):
@@ -69,9 +74,11 @@ def _split_ok(t2, h):
         os.environ.get('TDR_DWSG_TWO_PASS', '0') != '1'
 
 
-def ffn_fwd(yn, P, res=None):
-    """FeedForward.forward (:240-253)."""
+def ffn_fwd(yn, P, res=None, keep=True):
+    """FeedForward.forward (:240-253).  keep=False: (out, None); t2 goes after the first depthwise pair, x1 / x2 after the second"""
     t2 = R._pw_fwd(yn, P, 'ffn.project_in')                                         # [N, 2h, H, W]
+    if not keep:
+        yn = None
     h = t2.shape[1] // 2
     # x1 = [a3[:h] | a5[:h]], x2 = [a3[h:] | a5[h:]] (:244-247) are written in place: the 3x3 stencil owns the plane pair (c, c + h)
     # and stores its two planes to x1 / x2; the 5x5 conv runs per half.  a3 / a5 only exist as these slices.
@@ -87,6 +94,15 @@ def ffn_fwd(yn, P, res=None):
         a5 = K.dwk_fwd(t2, w5, b5, relu=True)
         x1 = K.concat2(a3[:, :h], a5[:, :h])
         x2 = K.concat2(a3[:, h:], a5[:, h:])
+    if not keep:
+        N2, H2, W2, dev = t2.shape[0], t2.shape[2], t2.shape[3], t2.device
+        t2 = a3 = a5 = None
+        cat = torch.empty(N2, 2 * h, H2, W2, dtype=torch.float32, device=dev)
+        K.dwk_fwd(x1, P['ffn.dwconv3x3_1.weight'], P.get('ffn.dwconv3x3_1.bias'), relu=True, out=cat[:, :h])
+        x1 = None
+        K.dwk_fwd(x2, P['ffn.dwconv5x5_1.weight'], P.get('ffn.dwconv5x5_1.bias'), relu=True, out=cat[:, h:])
+        x2 = None
+        return R._pw_fwd(cat, P, 'ffn.project_out', res=res), None
     cat = torch.empty(t2.shape[0], 2 * h, t2.shape[2], t2.shape[3], dtype=torch.float32, device=t2.device)
     z1 = K.dwk_fwd(x1, P['ffn.dwconv3x3_1.weight'], P.get('ffn.dwconv3x3_1.bias'), relu=True, out=cat[:, :h])   # straight into
     z2 = K.dwk_fwd(x2, P['ffn.dwconv5x5_1.weight'], P.get('ffn.dwconv5x5_1.bias'), relu=True, out=cat[:, h:])   # the concatenation
@@ -132,7 +148,11 @@ def ffn_bwd(dout, P, saved, G):
     return R._pw_bwd(K.add_(dt2, dt2b), yn, P, 'ffn.project_in', G)
 
 
-def tblock_fwd(x, P, heads, ln_type):
+def tblock_fwd(x, P, heads, ln_type, keep=True):
+    if not keep:                       # (out, None): the normalised tensors belong to attn_fwd / ffn_fwd, which let them go
+        y, _ = attn_fwd(R._ln_fwd(x, P, 'norm1.', ln_type)[0], P, heads, res=x, keep=False)
+        out, _ = ffn_fwd(R._ln_fwd(y, P, 'norm2.', ln_type)[0], P, res=y, keep=False)
+        return out, None
     xn, mu1, rs1 = R._ln_fwd(x, P, 'norm1.', ln_type)
     y, sv_a = attn_fwd(xn, P, heads, res=x)
     yn, mu2, rs2 = R._ln_fwd(y, P, 'norm2.', ln_type)
@@ -157,16 +177,16 @@ def tblock_bwd(dout, P, heads, ln_type, saved):
 # ---------------------------------------------------------------------------
 def _stage(fn, pre):
     """mefc_fwd / mefc_bwd on the sub-network `pre` as a stage of the walk (restormer_engine.walk_fwd / walk_bwd)"""
-    return lambda x, P, cfg, *rest: fn(x, P, pre, *rest)
+    return lambda x, P, cfg, *rest, **kw: fn(x, P, pre, *rest, **kw)
 
 
-def net_fwd(P, cfg, inp, ref):
-    """ref = None: the UN-GUIDED `DRSformer` of the same file (network_drsformer_guided_arch.py:586-676): no MASA pyramid, no
+def net_fwd(P, cfg, inp, ref, keep=True):
+    """keep=False: (out, None), nothing kept for a backward pass (restormer_engine.walk_fwd).  ref = None: the UN-GUIDED `DRSformer` of the same file (network_drsformer_guided_arch.py:586-676): no MASA pyramid, no
     fusion blocks, no padding (its PixelUnshuffle raises on sizes that are not multiples of 8), MEFC sub-networks always."""
     full = bool(cfg.get('mefc'))       # DRSformerRefFusion: MEFC sub-networks + a working level-1 fusion; else the 200L_SPA class
     return R.walk_fwd(P, cfg, inp, ref, 'DRSformer: H, W must be multiples of 8 (three PixelUnshuffle(2) stages); got {}x{}', tblock_fwd,
                       fuse=range(4) if full else range(1, 4),       # R6 (200L_SPA): the level-1 fusion is discarded; not computed here
-                      head=_stage(mefc_fwd, 'encoder_level0.') if full else None, tail=_stage(mefc_fwd, 'refinement.') if full else None)
+                      head=_stage(mefc_fwd, 'encoder_level0.') if full else None, tail=_stage(mefc_fwd, 'refinement.') if full else None, keep=keep)
 
 
 def net_bwd(dout, P, cfg, saved, G=None):
@@ -217,9 +237,10 @@ def _op_bwd(do, x, P, pre, j, sv, G):
     return dx
 
 
-def mefc_fwd(x, P, pre):
+def mefc_fwd(x, P, pre, keep=True):
     """x [N,C,H,W] -> subnet(x).  Gating: mean_hw -> Linear -> ReLU -> Linear -> softmax over the 8 operations of each step;
-    the per-image operation weights scale the (saved, unscaled) operation outputs while they are copied into the concat."""
+    the per-image operation weights scale the (saved, unscaled) operation outputs while they are copied into the concat.
+    keep=False: (out, None); an operation's output goes once it is copied into the concat, a step's concat after its `_out` conv"""
     N, C, H, W = x.shape
     nops = len(OPS)
     emb = K.plane_mean(x)
@@ -236,12 +257,15 @@ def mefc_fwd(x, P, pre):
         for j in range(nops):
             o, sv = _op_fwd(s0, P, f'{g}_ops.{i}._ops.{j}.', j)
             K.scale_copy(o, wflat[i * nops + j:], STEPS * nops, cat[:, j * C:(j + 1) * C])
-            ops.append((o, sv))
+            if keep:
+                ops.append((o, sv))
+            o = sv = None
         t = _pw(cat, P[f'{g}_ops.{i}._out.0.weight'], relu=True)
         s1 = K.add_relu(t, s0)
-        steps.append((s0, cat, t, s1, ops))
-        s0 = s1
-    return s0, (x, emb, h1, wts, steps)
+        if keep:
+            steps.append((s0, cat, t, s1, ops))
+        s0, cat, t, s1 = s1, None, None, None
+    return s0, ((x, emb, h1, wts, steps) if keep else None)
 
 
 def mefc_bwd(dout, P, pre, saved, G):

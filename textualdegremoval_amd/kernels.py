@@ -1638,6 +1638,17 @@ def mdta_softmax(G, ss, temp, heads):
     return A, AT
 
 
+def attn_fold_proj(AT, w_out, heads):
+    """AT [N,Cp,Cp] (mdta_softmax / tksa_softmax), w_out [C,C,1,1] (attn.project_out.weight) -> Wf [N,Cp,Cp] packed 1x1 weights
+    of project_out o attn: conv_forward with wp = Wf computes Wo (A v) without forming A v (forward-only, include/tdr.h)"""
+    N, Cp = AT.shape[0], AT.shape[-1]
+    Cc = w_out.shape[0]
+    assert AT.is_contiguous() and w_out.is_contiguous() and AT.shape[1] == Cp == mdta_pad(Cc) and w_out.shape[1] == Cc
+    Wf = torch.empty_like(AT)
+    check(_lib.load().tdr_attn_fold_proj(AT.data_ptr(), w_out.data_ptr(), N, Cc, heads, Wf.data_ptr(), _stream()), 'tdr_attn_fold_proj')
+    return Wf
+
+
 def mdta_bwd(G, ss, temp, A, dA, heads):
     """-> (W [N,Wp,Wp] packed weights of d[q;k] = W [q;k], dtemp [heads,1,1])"""
     N, Cc = G.shape[0], G.shape[-1]

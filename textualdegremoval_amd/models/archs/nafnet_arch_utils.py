@@ -1,5 +1,6 @@
 """LayerNorm2d on the HIP kernels.  Mirrors models/archs/nafnet_arch_utils.py:264-300
-of the reference (same class names, parameters `weight`/`bias`, eps 1e-6)."""
+of the reference (same class names, parameters `weight`/`bias`, eps 1e-6).  Also what every arch module shares: the device check
+and the no-gradient forward route (infer_fwd)."""
 import torch
 import torch.nn as nn
 
@@ -10,6 +11,25 @@ def require_gpu(t, what):
     if not t.is_cuda:
         raise RuntimeError(f'{what}: the HIP path needs tensors on the MI355X; there is no CPU fallback '
                            '(the CPU oracle lives in oracle/ and is test infrastructure only).')
+
+
+def infer_fwd(what, fwd, names, params, cfg, *images):
+    """the forward pass when no gradient can be asked of its result -- grad mode is off (`torch.no_grad()`, as in torch; `.eval()`
+    alone does not select it), or neither an image nor a parameter requires grad: the engine's whole-network forward `fwd` (net_fwd /
+    unet_fwd of engine, restormer_engine, promptir_engine, drsformer_engine) with keep=False, outside autograd -> the output alone, or
+    None when a gradient may be asked.  An image may be None (the un-guided networks of the Restormer family: ref=None).
+    The weights are packed afresh from the parameters as they are now, outside any kernels.PackPlan: a validation pass between two
+    optimiser steps must neither read a training step's cached packs nor record its own weights into that step's plan."""
+    if torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in images) or any(p.requires_grad for p in params)):
+        return None
+    require_gpu(images[0], what)
+    P = dict(zip(names, [p.detach() for p in params]))
+    prev = K.set_pack_plan(None)
+    try:
+        with torch.no_grad():
+            return fwd(P, cfg, *[t if t is None else t.detach() for t in images], keep=False)[0]
+    finally:
+        K.set_pack_plan(prev)
 
 
 class LayerNormFunction(torch.autograd.Function):

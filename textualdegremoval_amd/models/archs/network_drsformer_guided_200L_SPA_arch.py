@@ -15,7 +15,7 @@ import torch.nn as nn
 from ... import drsformer_engine as DE
 from ... import kernels as K
 from ... import restormer_engine as R
-from .nafnet_arch_utils import require_gpu
+from .nafnet_arch_utils import infer_fwd, require_gpu
 from .network_restormer_guided_arch import Downsample, Encoder, LayerNorm, OverlapPatchEmbed, Upsample, _named  # noqa: F401
 
 
@@ -181,4 +181,5 @@ class DRSformer200L_SPA_RefFusion(nn.Module):
 
     def forward(self, inp_img, ref_img):
         names, params = zip(*self.used_named_parameters())
-        return _NetFn.apply(inp_img, ref_img, list(names), self.cfg, *params)
+        out = infer_fwd('DRSformer200L_SPA_RefFusion', DE.net_fwd, names, params, self.cfg, inp_img, ref_img)
+        return out if out is not None else _NetFn.apply(inp_img, ref_img, list(names), self.cfg, *params)

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from ... import drsformer_engine as DE
 from ... import kernels as K
-from .nafnet_arch_utils import require_gpu
+from .nafnet_arch_utils import infer_fwd, require_gpu
 from .network_drsformer_guided_200L_SPA_arch import TransformerBlock, TransformerResFusionBlock
 from .network_restormer_guided_arch import Downsample, Encoder, OverlapPatchEmbed, Upsample, _named  # noqa: F401
 
@@ -176,7 +176,8 @@ class DRSformer(nn.Module):
 
     def forward(self, inp_img):
         names, params = _named(self)
-        return _NetFn.apply(inp_img, None, names, self.cfg, *params)
+        out = infer_fwd('DRSformer', DE.net_fwd, names, params, self.cfg, inp_img, None)
+        return out if out is not None else _NetFn.apply(inp_img, None, names, self.cfg, *params)
 
 
 class DRSformerRefFusion(nn.Module):
@@ -239,4 +240,5 @@ class DRSformerRefFusion(nn.Module):
 
     def forward(self, inp_img, ref_img):
         names, params = _named(self)
-        return _NetFn.apply(inp_img, ref_img, names, self.cfg, *params)
+        out = infer_fwd('DRSformerRefFusion', DE.net_fwd, names, params, self.cfg, inp_img, ref_img)
+        return out if out is not None else _NetFn.apply(inp_img, ref_img, names, self.cfg, *params)

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from ... import engine as E
-from .nafnet_arch_utils import LayerNorm2d, require_gpu
+from .nafnet_arch_utils import LayerNorm2d, infer_fwd as _infer_fwd, require_gpu
 
 
 def _named(module):
@@ -93,25 +93,6 @@ class _UNetFn(torch.autograd.Function):
         dinp, G = E.unet_bwd(dout, ctx.P, ctx.cfg, ctx.saved)
         ctx.saved = None
         return (dinp, None, None) + tuple(G[k] for k in ctx.names)
-
-
-def _infer_fwd(what, fwd, names, params, cfg, *images):
-    """the forward pass when no gradient can be asked of its result -- grad mode is off (`torch.no_grad()`, as in torch; `.eval()`
-    alone does not select it), or neither an image nor a parameter requires grad: engine.net_fwd / unet_fwd with keep=False, outside
-    autograd -> the output alone (bit-identical to the autograd node's), or None when a gradient may be asked.
-    The weights are packed afresh from the parameters as they are now, outside any kernels.PackPlan: a validation pass between two
-    optimiser steps must neither read a training step's cached packs nor record its own weights into that step's plan."""
-    if torch.is_grad_enabled() and (any(t.requires_grad for t in images) or any(p.requires_grad for p in params)):
-        return None
-    from ... import kernels as K
-    require_gpu(images[0], what)
-    P = dict(zip(names, [p.detach() for p in params]))
-    prev = K.set_pack_plan(None)
-    try:
-        with torch.no_grad():
-            return fwd(P, cfg, *[t.detach() for t in images], keep=False)[0]
-    finally:
-        K.set_pack_plan(prev)
 
 
 def make_layer(block, n_layers):

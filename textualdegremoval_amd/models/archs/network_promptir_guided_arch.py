@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from ... import kernels as K
 from ... import promptir_engine as PE
-from .nafnet_arch_utils import require_gpu
+from .nafnet_arch_utils import infer_fwd, require_gpu
 from .network_restormer_guided_arch import (Attention, BiasFree_LayerNorm, Downsample, Encoder, FeedForward,  # noqa: F401
                                             LayerNorm, OverlapPatchEmbed, ResidualBlock, TransformerBlock,
                                             TransformerResFusionBlock, Upsample, WithBias_LayerNorm, _named, make_layer)
@@ -142,7 +142,8 @@ class PromptIR(nn.Module):
 
     def forward(self, inp_img, noise_emb=None):
         names, params = zip(*self.used_named_parameters())
-        return _NetFn.apply(inp_img, None, list(names), self.cfg, *params)
+        out = infer_fwd('PromptIR', PE.net_fwd, names, params, self.cfg, inp_img, None)
+        return out if out is not None else _NetFn.apply(inp_img, None, list(names), self.cfg, *params)
 
 
 class PromptIRRefFusion(nn.Module):
@@ -239,4 +240,5 @@ class PromptIRRefFusion(nn.Module):
 
     def forward(self, inp_img, ref_img, noise_emb=None):
         names, params = zip(*self.used_named_parameters())
-        return _NetFn.apply(inp_img, ref_img, list(names), self.cfg, *params)
+        out = infer_fwd('PromptIRRefFusion', PE.net_fwd, names, params, self.cfg, inp_img, ref_img)
+        return out if out is not None else _NetFn.apply(inp_img, ref_img, list(names), self.cfg, *params)

@@ -15,7 +15,7 @@ import torch.nn as nn
 from ... import engine as E
 from ... import kernels as K
 from ... import restormer_engine as R
-from .nafnet_arch_utils import require_gpu
+from .nafnet_arch_utils import infer_fwd, require_gpu
 
 
 def _named(module):
@@ -281,7 +281,8 @@ class Restormer(nn.Module):
 
     def forward(self, inp_img):
         names, params = _named(self)
-        return _UNetFn.apply(inp_img, names, self.cfg, *params)
+        out = infer_fwd('Restormer', R.net_fwd, names, params, self.cfg, inp_img, None)
+        return out if out is not None else _UNetFn.apply(inp_img, names, self.cfg, *params)
 
 
 class RestormerRefFusion(nn.Module):
@@ -349,4 +350,5 @@ class RestormerRefFusion(nn.Module):
 
     def forward(self, inp_img, ref_img):
         names, params = _named(self)
-        return _NetFn.apply(inp_img, ref_img, names, self.cfg, *params)
+        out = infer_fwd('RestormerRefFusion', R.net_fwd, names, params, self.cfg, inp_img, ref_img)
+        return out if out is not None else _NetFn.apply(inp_img, ref_img, names, self.cfg, *params)

@@ -17,9 +17,9 @@ from . import restormer_engine as R
 # ---------------------------------------------------------------------------
 # PromptGenBlock (:417-441)
 # ---------------------------------------------------------------------------
-def prompt_fwd(x, P, pre):
+def prompt_fwd(x, P, pre, keep=True):
     """x [N,C,H,W] -> prompt [N,D,H,W].  The softmax-weighted sum over the L components and the bilinear resize are both
-    linear and commute: the L*D parameter planes are resized once per call, not once per image."""
+    linear and commute: the L*D parameter planes are resized once per call, not once per image.  keep=False: (prompt, None)"""
     N, C, H, W = x.shape
     comp = P[pre + 'prompt_param'][0]                                   # [L, D, S, S]
     L, D, S, _ = comp.shape
@@ -28,7 +28,7 @@ def prompt_fwd(x, P, pre):
     Pi = comp if (H, W) == (S, S) else K.resize_bilinear(comp.contiguous(), H, W)
     mix = K.prompt_mix_fwd(w, Pi.contiguous())
     out = E.conv_fwd(mix, P[pre + 'conv3x3.weight'], None, 1, 1)
-    return out, (x.shape, emb, w, Pi, mix)
+    return out, ((x.shape, emb, w, Pi, mix) if keep else None)
 
 
 def prompt_bwd(dout, P, pre, saved, G):
@@ -45,14 +45,17 @@ def prompt_bwd(dout, P, pre, saved, G):
     return demb, 1.0 / (H * W)
 
 
-def _prompt_stage_fwd(x, P, cfg, k):
+def _prompt_stage_fwd(x, P, cfg, k, keep=True):
     """the walk's stage before the Upsample into decoder level k (:1057-1084): cat([x, prompt_k(x)]) -> noise_level_k
-    (TransformerBlock; all three use heads[2], :736, :747, :757) -> reduce_noise_level_k (1x1)"""
-    pr, sv_p = prompt_fwd(x, P, f'prompt{k}.')
-    cat = K.concat2(x, pr)
-    t, sv_t = R.tblock_fwd(cat, E._sub(P, f'noise_level{k}.'), cfg['heads'][2], cfg['LayerNorm_type'])
+    (TransformerBlock; all three use heads[2], :736, :747, :757) -> reduce_noise_level_k (1x1).  keep=False: (y, None)"""
+    kw = R._kw(keep)
+    pr, sv_p = prompt_fwd(x, P, f'prompt{k}.', **kw)
+    cat = [K.concat2(x, pr)]
+    if not keep:
+        pr = None
+    t, sv_t = R.tblock_fwd(E._take(cat, 0) if not keep else cat[0], E._sub(P, f'noise_level{k}.'), cfg['heads'][2], cfg['LayerNorm_type'], **kw)
     y = R._pw_fwd(t, P, f'reduce_noise_level{k}')
-    return y, (x.shape[1], sv_p, sv_t, t)
+    return y, ((x.shape[1], sv_p, sv_t, t) if keep else None)
 
 
 def _prompt_stage_bwd(d, P, cfg, k, saved, G):
@@ -70,14 +73,14 @@ def _prompt_stage_bwd(d, P, cfg, k, saved, G):
 # ---------------------------------------------------------------------------
 # whole network  PromptIRRefFusion.forward (:864-1092): restormer_engine's walk with the prompt stages and the refinement blocks
 # ---------------------------------------------------------------------------
-def net_fwd(P, cfg, inp, ref):
-    """ref = None: the UN-GUIDED `PromptIR` of the same file (:443-590): no MASA pyramid, no fusion blocks, no padding (sizes must
+def net_fwd(P, cfg, inp, ref, keep=True):
+    """keep=False: (out, None), nothing kept for a backward pass (restormer_engine.walk_fwd).  ref = None: the UN-GUIDED `PromptIR` of the same file (:443-590): no MASA pyramid, no fusion blocks, no padding (sizes must
     be multiples of 8).  Like the guided class it only exists as decoder=True, dim = 48 (with decoder=False its up4_3 receives
     the 384-channel latent on a 192-channel convolution and the reference raises: R4)."""
     if not cfg.get('decoder', True) or cfg['dim'] != 48 or (ref is not None and cfg['nf'] != 48):
         raise ValueError('PromptIR(-ref) exists only as decoder=True, dim = nf = 48 (the reference raises otherwise: defect R4)')
     return R.walk_fwd(P, cfg, inp, ref, 'PromptIR: H, W must be multiples of 8 (three PixelUnshuffle(2) stages); got {}x{}',
-                      pre_up=_prompt_stage_fwd, tail=R.refine_fwd)
+                      pre_up=_prompt_stage_fwd, tail=R.refine_fwd, keep=keep)
 
 
 def net_bwd(dout, P, cfg, saved, G=None):

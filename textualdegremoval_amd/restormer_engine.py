@@ -32,11 +32,20 @@ from .kernels import EPI_PSHUF, PACK_DGRAD_S1, PACK_FWD
 
 LN_EPS = 1e-5        # :190,208
 PADDER_LOG2 = 3      # self.padder_size = 2 ** 3 (:546)
+# a forward pass that keeps nothing (keep=False) folds attn.project_out into the per-image attention weights (kernels.attn_fold_proj):
+# Wo (A v) = (Wo A) v, one 1x1 convolution and no `o` plane; False: the unfolded launches of the training forward, `o` dropped after
+# project_out -- the bits of keep=True (module switch for A/B runs, profiles/probe_restormer_infer.py; not an environment knob)
+INFER_FOLD = True
 
 
 # ---------------------------------------------------------------------------
 # small helpers
 # ---------------------------------------------------------------------------
+def _kw(keep):
+    """what a stage callable is called with: nothing more than before when everything is kept, `keep=False` otherwise"""
+    return {} if keep else {'keep': False}
+
+
 def _ln_fwd(x, P, pre, ln_type):
     """LayerNorm (:211-218): BiasFree (:172-190) scales the uncentred x; WithBias (:193-208)."""
     center = ln_type != 'BiasFree'
@@ -72,35 +81,60 @@ def _pw_bwd(dout, x, P, name, G):
     return K.conv_forward(dout, wp, mp, Cin, 1)
 
 
-def _img_conv(x, Wt, Cout, out=None):
+def _img_conv(x, Wt, Cout, out=None, bias=None, res=None):
     """1x1 conv with per-image weights Wt [N, Kp, Mp] (fp32 packed layout emitted by tdr_mdta_*): on the split-bf16
     kernel after one batched re-pack, or directly on the exact fp32 kernel (kernels.MATH)."""
     Kp, Mp = Wt.shape[-2], Wt.shape[-1]
     if K.MATH != 'f32':
         pw, per_b = K.pack_f32packed_to_bx3(Wt)
-        return K.conv_forward(x, pw, Mp, Cout, 1, wp_ns=per_b, out=out)
-    return K.conv_forward(x, Wt, Mp, Cout, 1, wp_ns=Kp * Mp, out=out)
+        return K.conv_forward(x, pw, Mp, Cout, 1, wp_ns=per_b, out=out, bias=bias, res=res)
+    return K.conv_forward(x, Wt, Mp, Cout, 1, wp_ns=Kp * Mp, out=out, bias=bias, res=res)
+
+
+def attn_tail_fwd(v, AT, P, heads, res, keep=True):
+    """project_out(attn v) + res, the end of MDTA / TKSA.  v [N,C,H,W] (a channel slice of qkv), AT [N,Cp,Cp] -> (y, o); o = attn v is
+    what project_out's weight gradient reads.  keep=False with INFER_FOLD: y = (Wo attn) v + bias + res in one convolution on the folded
+    per-image weights, o never formed -> (y, None).  In every kernels.MATH but 'f32' the per-image weights run on the 3-way bf16 split
+    (fp32 exponent range), so Wo attn -- which has Wo's range, not attn's [0, 1] -- sits in the operand window of each mode."""
+    Cc = v.shape[1]
+    if not keep and INFER_FOLD:
+        return _img_conv(v, K.attn_fold_proj(AT, P['attn.project_out.weight'], heads), Cc, bias=P.get('attn.project_out.bias'), res=res), None
+    o = _img_conv(v, AT, Cc)                                                     # attn v
+    return _pw_fwd(o, P, 'attn.project_out', res=res), (o if keep else None)
 
 
 # ---------------------------------------------------------------------------
 # TransformerBlock (:318-331) = x + MDTA(LN(x)); + GDFN(LN(.))
 # ---------------------------------------------------------------------------
-def tblock_fwd(x, P, heads, ln_type):
+def tblock_fwd(x, P, heads, ln_type, keep=True):
+    """keep=False: a forward pass no backward follows -> (out, None); each intermediate goes once its last consumer is enqueued (live
+    at the widest point, in planes of the block's C channels: x, y, t2 [5.32] and g [2.66]), and the attention tail is attn_tail_fwd's"""
     N, Cc, H, W = x.shape
     xn, mu1, rs1 = _ln_fwd(x, P, 'norm1.', ln_type)
     # ---- MDTA (:246-277)
     t = _pw_fwd(xn, P, 'attn.qkv')                                               # [N,3C,H,W]
+    if not keep:
+        xn = mu1 = rs1 = None
     qkv = K.dwconv_fwd(t, P['attn.qkv_dwconv.weight'], P.get('attn.qkv_dwconv.bias'))
+    if not keep:
+        t = None
     ss = K.row_sumsq(qkv, 2 * Cc)                                                # |q_i|^2, |k_j|^2
     Gm = K.conv_wgrad(qkv[:, Cc:2 * Cc], qkv[:, :Cc], Cc, Cc, 1, per_image=True, fp16_range=True).view(N, Cc, Cc)   # q k^T
     A, AT = K.mdta_softmax(Gm, ss, P['attn.temperature'], heads)
-    o = _img_conv(qkv[:, 2 * Cc:], AT, Cc)                                       # attn v
-    y = _pw_fwd(o, P, 'attn.project_out', res=x)
+    y, o = attn_tail_fwd(qkv[:, 2 * Cc:], AT, P, heads, x, keep)
+    if not keep:
+        qkv = ss = Gm = A = AT = None
     # ---- GDFN (:223-241)
     yn, mu2, rs2 = _ln_fwd(y, P, 'norm2.', ln_type)
     t2 = _pw_fwd(yn, P, 'ffn.project_in')                                        # [N,2h,H,W]
+    if not keep:
+        yn = mu2 = rs2 = None
     g = K.dwgelu_fwd(t2, P['ffn.dwconv.weight'], P.get('ffn.dwconv.bias'))
+    if not keep:
+        t2 = None
     out = _pw_fwd(g, P, 'ffn.project_out', res=y)
+    if not keep:
+        return out, None
     return out, (x, xn, mu1, rs1, t, qkv, ss, Gm, A, o, y, yn, mu2, rs2, t2, g)
 
 
@@ -135,9 +169,9 @@ def tblock_bwd(dout, P, heads, ln_type, saved):
 
 # TransformerResFusionBlock (:334-353): block(x) * alpha + x, around the network's TransformerBlock pair (tblock_fwd / tblock_bwd
 # here, drsformer_engine's TKSA / MSFN blocks there)
-def fblock_fwd(x, P, heads, ln_type, tblock=tblock_fwd):
-    z, sv = tblock(x, P, heads, ln_type)
-    return K.axpby_dev(z, P['alpha'], x), (sv, z)
+def fblock_fwd(x, P, heads, ln_type, tblock=tblock_fwd, keep=True):
+    z, sv = tblock(x, P, heads, ln_type, **_kw(keep))
+    return K.axpby_dev(z, P['alpha'], x), ((sv, z) if keep else None)
 
 
 def fblock_bwd(dout, P, heads, ln_type, saved, tblock=tblock_bwd):
@@ -152,13 +186,13 @@ def fblock_bwd(dout, P, heads, ln_type, saved, tblock=tblock_bwd):
     return dx, G
 
 
-def seq_fwd(x, P, pre, n, heads, ln_type, tblock=tblock_fwd, fusion=False):
-    saved = []
+def seq_fwd(x, P, pre, n, heads, ln_type, tblock=tblock_fwd, fusion=False, keep=True):
+    saved, kw = [], _kw(keep)
     for i in range(n):
         Pi = E._sub(P, f'{pre}{i}.')
-        x, sv = fblock_fwd(x, Pi, heads, ln_type, tblock) if fusion else tblock(x, Pi, heads, ln_type)
+        x, sv = fblock_fwd(x, Pi, heads, ln_type, tblock, **kw) if fusion else tblock(x, Pi, heads, ln_type, **kw)
         saved.append(sv)
-    return x, saved
+    return x, (saved if keep else None)
 
 
 def seq_bwd(d, P, pre, n, heads, ln_type, saved, G, tblock=tblock_bwd, fusion=False):
@@ -171,9 +205,9 @@ def seq_bwd(d, P, pre, n, heads, ln_type, saved, G, tblock=tblock_bwd, fusion=Fa
     return d
 
 
-def refine_fwd(x, P, cfg):
+def refine_fwd(x, P, cfg, keep=True):
     """the `refinement.` TransformerBlocks after decoder_level1 (Restormer, PromptIR): a `tail` stage of walk_fwd"""
-    return seq_fwd(x, P, 'refinement.', cfg['num_refinement_blocks'], cfg['heads'][0], cfg['LayerNorm_type'])
+    return seq_fwd(x, P, 'refinement.', cfg['num_refinement_blocks'], cfg['heads'][0], cfg['LayerNorm_type'], keep=keep)
 
 
 def refine_bwd(d, P, cfg, saved, G):
@@ -221,7 +255,8 @@ _DOWN = ['down1_2.body.0.weight', 'down2_3.body.0.weight', 'down3_4.body.0.weigh
 _UP = ['up2_1.body.0.weight', 'up3_2.body.0.weight', 'up4_3.body.0.weight']        # _UP[l]: into decoder level l + 1
 
 
-def walk_fwd(P, cfg, inp, ref, size_msg, tblock=tblock_fwd, fuse=range(4), head=None, pre_up=None, tail=None, dual_pixel=False):
+def walk_fwd(P, cfg, inp, ref, size_msg, tblock=tblock_fwd, fuse=range(4), head=None, pre_up=None, tail=None, dual_pixel=False,
+             keep=True):
     """inp [N,C,H,W] -> (out, saved).
     ref [N,C,Hr,Wr]: guided -- MASA pyramids and match (engine.pyramids_fwd / masa_fwd), zero padding to the MASA block grid
     (reference defect R1: the pyramid is [L1..L4], padder_size 8), a fusion stage (fusion blocks on cat[x, warp_l], then the
@@ -233,51 +268,77 @@ def walk_fwd(P, cfg, inp, ref, size_msg, tblock=tblock_fwd, fuse=range(4), head=
       pre_up(x, P, cfg, l) stage before the Upsample into decoder level l (l = 3, 2, 1) -> (x, saved)
       tail(x, P, cfg)      stage after decoder_level1 -> (x, saved)
       dual_pixel           output(x + skip_conv(inp_enc_level1)) without `+ inp` (Restormer's dual-pixel task, :955-959)
-    saved = (N, (H0, W0, Hp, Wp), geo, pyr, None, None, sv_masa, S) -- the prefix of engine.net_fwd's; S holds the rest by name."""
+    saved = (N, (H0, W0, Hp, Wp), geo, pyr, None, None, sv_masa, S) -- the prefix of engine.net_fwd's; S holds the rest by name.
+    keep=False: a forward pass no backward follows (inference, validation) -> (out, None); tblock and the stages are called with
+    keep=False and return (x, None).  Live at any moment: the warped reference features of the levels still to come, the encoder outputs
+    of the levels passed (each until its decoder level has concatenated it), the padded input (the output conv's residual) and one
+    block's working set -- the pyramids go behind the transfer kernels, a concat buffer when the level's first fusion block has read it,
+    `inp_enc_level1` at once unless dual_pixel."""
     N = inp.shape[0]
+    kw = _kw(keep)
     if ref is not None:
-        pyr, sizes = E.pyramids_fwd(P, cfg, inp, ref, PADDER_LOG2, 4)
-        warp, sv_masa = E.masa_fwd(pyr.lq_deep, pyr.ref_feats, N, pyr.geo)
+        pyr, sizes = E.pyramids_fwd(P, cfg, inp, ref, PADDER_LOG2, 4, **kw)
+        warp, sv_masa = E.masa_fwd(pyr.lq_deep, pyr.ref_feats, N, pyr.geo, **kw)
+        if not keep:
+            pyr.lq_deep = pyr.ref_feats = None
+            warp = [w if l in fuse else None for l, w in enumerate(warp)]
     else:
         H, W = inp.shape[2:]
         if H % 8 or W % 8:
             raise ValueError(size_msg.format(H, W))
         pyr, sizes, sv_masa, fuse = types.SimpleNamespace(inp_p=inp.contiguous(), geo=None), (H, W, H, W), None, ()
     hd, ln, nb, nfz = cfg['heads'], cfg['LayerNorm_type'], cfg['num_blocks'], cfg.get('reffusion_n_blocks')
-    S = types.SimpleNamespace(head=None, levels=[], enc=[], dec=[None] * 3, tail=None)
+    S = types.SimpleNamespace(levels=[], dec=[None] * 3) if keep else None      # what walk_bwd reads, by name
+    enc, x_l1, sv_h, sv_t = [], None, None, None
     x = E.conv_fwd(pyr.inp_p, P['patch_embed.proj.weight'], P.get('patch_embed.proj.bias'), 1, 1)
     if head:
-        x, S.head = head(x, P, cfg)
+        x, sv_h = head(x, P, cfg, **kw)
     for l in range(4):
         sv_f = None
         if l in fuse:
-            f, sv_f = seq_fwd(K.concat2(x, warp[l]), P, _FUS[l], nfz[l], hd[l], ln, tblock, fusion=True)
-            x = K.slice_channels(f, 0, x.shape[1])         # `[:, :embed_dim // 2]` (:892,903,914,925)
-        if l == 0:
-            S.x_l1 = x                                     # `inp_enc_level1`: what skip_conv reads when dual_pixel
-        e, sv_e = seq_fwd(x, P, _ENC[l], nb[l], hd[l], ln, tblock)
-        S.enc.append(e)
-        S.levels.append((sv_f, sv_e))
+            arg, c = [K.concat2(x, warp[l])], x.shape[1]
+            if not keep:
+                x = warp[l] = None
+            f, sv_f = seq_fwd(E._take(arg, 0), P, _FUS[l], nfz[l], hd[l], ln, tblock, fusion=True, **kw)
+            x = K.slice_channels(f, 0, c)                  # `[:, :embed_dim // 2]` (:892,903,914,925)
+            f = None
+        if l == 0 and (keep or dual_pixel):
+            x_l1 = x                                       # `inp_enc_level1`: what skip_conv reads when dual_pixel
+        arg = [x]
+        if not keep:
+            x = None
+        e, sv_e = seq_fwd(E._take(arg, 0), P, _ENC[l], nb[l], hd[l], ln, tblock, **kw)
+        enc.append(e if keep or l < 3 else None)
+        if keep:
+            S.levels.append((sv_f, sv_e))
         if l < 3:
             x = down_fwd(e, P[_DOWN[l]])
-    x = e                                                  # the latent
+    x, e = e, None                                         # the latent
     for l in (2, 1, 0):                                    # decoder level l + 1 on cat[Upsample(x), encoder level l + 1]
         sv_p = None
         if pre_up:
-            x, sv_p = pre_up(x, P, cfg, l + 1)
-        cat = K.concat2(up_fwd(x, P[_UP[l]]), S.enc[l])
-        y, sv_d = seq_fwd(_pw_fwd(cat, P, f'reduce_chan_level{l + 1}') if l else cat, P, f'decoder_level{l + 1}.', nb[l], hd[l], ln,
-                          tblock)
-        S.dec[l] = (sv_p, x, cat, sv_d)
+            x, sv_p = pre_up(x, P, cfg, l + 1, **kw)
+        cat = K.concat2(up_fwd(x, P[_UP[l]]), enc[l])
+        arg = [_pw_fwd(cat, P, f'reduce_chan_level{l + 1}') if l else cat]
+        if not keep:
+            x = cat = enc[l] = None
+        y, sv_d = seq_fwd(E._take(arg, 0), P, f'decoder_level{l + 1}.', nb[l], hd[l], ln, tblock, **kw)
+        if keep:
+            S.dec[l] = (sv_p, x, cat, sv_d)
         x = y
+    y = None
     if tail:
-        x, S.tail = tail(x, P, cfg)
+        x, sv_t = tail(x, P, cfg, **kw)
     if dual_pixel:
-        x = _pw_fwd(S.x_l1, P, 'skip_conv', res=x)
-    S.y = x
+        x = _pw_fwd(x_l1, P, 'skip_conv', res=x)
+        if not keep:
+            x_l1 = None
     out_p = E.conv_fwd(x, P['output.weight'], P.get('output.bias'), 1, 1, res=None if dual_pixel else pyr.inp_p)
     H0, W0, Hp, Wp = sizes
     out = out_p if (Hp, Wp) == (H0, W0) else K.pad_crop(out_p, H0, W0)
+    if not keep:
+        return out, None
+    S.head, S.tail, S.enc, S.x_l1, S.y = sv_h, sv_t, enc, x_l1, x
     return out, (N, sizes, pyr.geo, pyr, None, None, sv_masa, S)
 
 
@@ -336,10 +397,11 @@ def walk_bwd(dout, P, cfg, saved, G=None, tblock=tblock_bwd, head=None, pre_up=N
 # ---------------------------------------------------------------------------
 # whole network: RestormerRefFusion (ref given) and the un-guided Restormer (ref None)
 # ---------------------------------------------------------------------------
-def net_fwd(P, cfg, inp, ref):
-    """inp, ref [N,3,H,W] -> (out [N,3,H,W], saved).  cfg: constructor kwargs of RestormerRefFusion / Restormer."""
+def net_fwd(P, cfg, inp, ref, keep=True):
+    """inp, ref [N,3,H,W] -> (out [N,3,H,W], saved).  cfg: constructor kwargs of RestormerRefFusion / Restormer.
+    keep=False: (out, None), nothing kept for a backward pass (walk_fwd)"""
     return walk_fwd(P, cfg, inp, ref, 'Restormer: H, W must be multiples of 8 (three PixelUnshuffle(2) stages, :370-378); got {}x{}',
-                    tail=refine_fwd, dual_pixel=cfg.get('dual_pixel_task'))
+                    tail=refine_fwd, dual_pixel=cfg.get('dual_pixel_task'), keep=keep)
 
 
 def net_bwd(dout, P, cfg, saved, G=None):
