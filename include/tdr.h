@@ -24,7 +24,7 @@ extern "C" {
  * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
  * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*); the
  * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
-#define TDR_ABI_VERSION 110
+#define TDR_ABI_VERSION 111
 int tdr_version(void);
 const char* tdr_last_error(void);
 
@@ -970,6 +970,46 @@ int tdr_modgate_fwd(const float* t, const float* a, const float* b, int64_t ab_n
                     void* stream);
 int tdr_modgate_bwd(const float* dg, const float* dgb, float dgb_mul, const float* t, const float* a, const float* b, int64_t ab_ns, int N,
                     int c, int HW, float* dt, float* da, float* db, int64_t d_ns, void* stream);
+/* ---------------------------------------------------------------------------
+ * NAFBlock_DynamicFusion for a forward pass that keeps nothing (inference), three launches per block (csrc/tdr_dyn_infer.hip, ABI 111):
+ *   tdr_dyn_head_infer   t1 = conv1(LayerNorm2d(x a0 + b0))                        -- the tile of tdr_naf_head_infer
+ *   tdr_dyn_dwsg_fwd     u = (dw3x3(t1) + b) a1 + b1 over 2C channels; g = u[:C] u[C:]; pooled [N][C] = mean g (fixed-order finish)
+ *   tdr_dyn_tail_infer   tdr_naf_tail_infer with t4 a2 + b2 ahead of the SimpleGate -- only `out` is written
+ * a*, b*: [N][.] rows with image stride ab_ns (slices of the tdr_kvproj_fwd output).  Supported: tdr_naf_tail_supported(C, HW) (for the
+ * stencil also W % 4 == 0), N <= 16; the weights of the chains are packed as for tdr_naf_head_fwd / tdr_naf_tail_fwd (w_fmt 1 or 2).
+ * Arguments are checked on the host before anything is launched. */
+typedef struct TdrDynHeadDesc {
+    int N, C, HW, w_fmt;
+    const float* x; int64_t x_ns;
+    const float *a0, *b0; int64_t ab_ns;     /* [N, C] rows */
+    const float *lnw, *lnb; float eps;
+    const void* w1; const float* b1;
+    float* t1; int64_t t1_ns;                /* [N, 2C, HW] */
+} TdrDynHeadDesc;
+int tdr_dyn_head_infer(const TdrDynHeadDesc* d, void* stream);
+typedef struct TdrDynDwsgDesc {
+    int N, C, H, W;
+    const float* t;                          /* [N, 2C, H, W] dense */
+    const float *w, *b;                      /* depthwise weight [2C, 9], bias [2C] */
+    const float *a1, *b1; int64_t ab_ns;     /* [N, 2C] rows */
+    float* g;                                /* [N, C, H, W] dense */
+    float* pooled;                           /* [N, C] */
+    float* ws;                               /* tdr_dyn_dwsg_ws_floats(N, C, H, W) floats */
+} TdrDynDwsgDesc;
+int64_t tdr_dyn_dwsg_ws_floats(int N, int C, int H, int W);
+int tdr_dyn_dwsg_fwd(const TdrDynDwsgDesc* d, void* stream);
+typedef struct TdrDynTailDesc {
+    int N, C, HW, w_fmt;
+    float eps;
+    const float* g;   int64_t g_ns;          /* [N, C, HW] */
+    const float* sca;                        /* [N, C] channel attention */
+    const float* x;   int64_t x_ns;          /* block input (residual) */
+    const void *w3, *w4, *w5;
+    const float *b3, *beta, *lnw, *lnb, *b4, *b5, *gamma;
+    const float *a2, *b2; int64_t ab_ns;     /* [N, 2C] rows */
+    float* out; int64_t out_ns;
+} TdrDynTailDesc;
+int tdr_dyn_tail_infer(const TdrDynTailDesc* d, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TDR_LIB_PATH', os.path.join(_HERE, 'libtdr_hip.so'))   # override: profiling probe builds
 
-ABI_VERSION = 110      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
+ABI_VERSION = 111      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
 c_fp = C.c_void_p      # device pointers travel as integers
 i32, i64, f32 = C.c_int, C.c_int64, C.c_float
 
@@ -112,6 +112,25 @@ class TdrNafHeadFwdDesc(C.Structure):
     _fields_ = [('N', i32), ('C', i32), ('HW', i32), ('w_fmt', i32),
                 ('x', c_fp), ('x_ns', i64), ('lnw', c_fp), ('lnb', c_fp), ('eps', f32), ('w1', c_fp), ('b1', c_fp),
                 ('mu', c_fp), ('rs', c_fp), ('xn', c_fp), ('xn_ns', i64), ('t1', c_fp), ('t1_ns', i64)]
+
+
+class TdrDynHeadDesc(C.Structure):
+    _fields_ = [('N', i32), ('C', i32), ('HW', i32), ('w_fmt', i32),
+                ('x', c_fp), ('x_ns', i64), ('a0', c_fp), ('b0', c_fp), ('ab_ns', i64), ('lnw', c_fp), ('lnb', c_fp), ('eps', f32),
+                ('w1', c_fp), ('b1', c_fp), ('t1', c_fp), ('t1_ns', i64)]
+
+
+class TdrDynDwsgDesc(C.Structure):
+    _fields_ = [('N', i32), ('C', i32), ('H', i32), ('W', i32),
+                ('t', c_fp), ('w', c_fp), ('b', c_fp), ('a1', c_fp), ('b1', c_fp), ('ab_ns', i64), ('g', c_fp), ('pooled', c_fp), ('ws', c_fp)]
+
+
+class TdrDynTailDesc(C.Structure):
+    _fields_ = [('N', i32), ('C', i32), ('HW', i32), ('w_fmt', i32), ('eps', f32),
+                ('g', c_fp), ('g_ns', i64), ('sca', c_fp), ('x', c_fp), ('x_ns', i64),
+                ('w3', c_fp), ('w4', c_fp), ('w5', c_fp),
+                ('b3', c_fp), ('beta', c_fp), ('lnw', c_fp), ('lnb', c_fp), ('b4', c_fp), ('b5', c_fp), ('gamma', c_fp),
+                ('a2', c_fp), ('b2', c_fp), ('ab_ns', i64), ('out', c_fp), ('out_ns', i64)]
 
 
 class TdrSfDynVecDesc(C.Structure):
@@ -348,6 +367,10 @@ SIGNATURES = {
     'tdr_nc_affine': (i32, [c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp]),
     'tdr_nc_affine_bwd': (i32, [c_fp, c_fp, c_fp, i64, c_fp, i32, i32, i32, c_fp, c_fp, c_fp, i64, c_fp]),
     'tdr_modgate_fwd': (i32, [c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp, c_fp]),
+    'tdr_dyn_head_infer': (i32, [C.POINTER(TdrDynHeadDesc), c_fp]),
+    'tdr_dyn_dwsg_ws_floats': (i64, [i32, i32, i32, i32]),
+    'tdr_dyn_dwsg_fwd': (i32, [C.POINTER(TdrDynDwsgDesc), c_fp]),
+    'tdr_dyn_tail_infer': (i32, [C.POINTER(TdrDynTailDesc), c_fp]),
     'tdr_modgate_bwd': (i32, [c_fp, c_fp, f32, c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp, c_fp, i64, c_fp]),
     'tdr_niqe_ws_floats': (i64, [i32, i32]),
     'tdr_niqe_features': (i32, [c_fp, i32, i32, i32, c_fp, c_fp, i32, c_fp, c_fp, c_fp]),

@@ -51,6 +51,18 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned (&p)[Sch
 
 constexpr int NPX = 64;                       // pixels per workgroup
 
+// The text-embedding modulated forward-only chains of NAFBlock_DynamicFusion (tdr_dyn_head_infer / tdr_dyn_tail_infer): this file compiled
+// a third time (tdr_dyn_infer.hip defines TDR_NAF_DYN_TU), the forward kernels with a per-(image, channel) affine on the x tile as it is
+// read (head) and on conv4's accumulators ahead of the gate (tail).  Off everywhere else: the other two units' kernels are untouched.
+#ifdef TDR_NAF_DYN_TU
+constexpr bool NAF_DYN = true;
+#else
+constexpr bool NAF_DYN = false;
+#endif
+// the modulation rows of image n (ma, mb: fields of the argument structs in the modulated unit alone, hence the dependent access)
+template <typename A> __device__ __forceinline__ const float* dyn_ma(const A& a, int n) { return a.ma + (long)n * a.m_ns; }
+template <typename A> __device__ __forceinline__ const float* dyn_mb(const A& a, int n) { return a.mb + (long)n * a.m_ns; }
+
 // Phase timeline (probe builds only: make probe -> libtdr_hip_probe.so with -DTDR_NB_PROBE; profiles/probe_nafblock_timeline.py):
 // s_memtime stamps of waves 0 and 5 of workgroups (0, 0) and (37, 2) at the phase boundaries of the chain kernels.
 #ifdef TDR_NB_PROBE
@@ -194,6 +206,9 @@ struct TailArgs {
     float* out; long out_ns;
     int HW;
     int c_out;                        // rows of conv5 actually produced (the `[:, :chan]` slice of the fusion blocks, :719,727)
+#ifdef TDR_NAF_DYN_TU
+    const float *ma, *mb; long m_ns;  // [N][2C] rows (image stride m_ns): t4 a + b ahead of the gate (sg2 of NAFBlock_DynamicFusion)
+#endif
 };
 
 // 2C threads = C/32 waves (C = 256: 8 waves, two per SIMD): wave w owns the 32 channels [32w, 32w + 32) of the C-row GEMMs and, in conv4,
@@ -370,6 +385,24 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
         });
     }
     NB_STAMP(4);
+    if constexpr (NAF_DYN) {
+        // u = (acc + b4) a + b = acc a + (b4 a + b): two values per row, one row tile at a time (the tile sits at the register limit here)
+        const float *pa = dyn_ma(a, n), *pb = dyn_mb(a, n);
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) {
+            float sv[16], tv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int ch = tm * C + m0 + row_of(r, kk);
+                sv[r] = pa[ch];
+                tv[r] = __builtin_fmaf(a.b4[ch], sv[r], pb[ch]);
+            }
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc4[tm][tn][r] = __builtin_fmaf(acc4[tm][tn][r], sv[r], tv[r]);
+        }
+    } else {
     float b4v[2][16];
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
@@ -381,6 +414,7 @@ __global__ __launch_bounds__(2 * C, 2) void naf_tail_fwd_kernel(TailArgs a) {
         for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc4[tm][tn][r] += b4v[tm][r];
+    }
     __syncthreads();                                          // every wave has finished reading the yn planes
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
@@ -456,6 +490,9 @@ struct HeadFwdArgs {
     float* xn; long xn_ns;
     float* t1; long t1_ns;
     int HW;
+#ifdef TDR_NAF_DYN_TU
+    const float *ma, *mb; long m_ns;  // [N][C] rows (image stride m_ns): the LayerNorm input is x a + b
+#endif
 };
 
 // KEEP = false (tdr_naf_head_infer): xn, mu and rs stay on the chip (NULL in HeadFwdArgs), t1 is the one tensor written -- same bits.
@@ -478,6 +515,23 @@ __global__ __launch_bounds__(2 * C, 2) void naf_head_fwd_kernel(HeadFwdArgs a) {
     float psum[2] = {0.f, 0.f};
     {
         const float* xp = a.x + (long)n * a.x_ns + p0 + j;
+        if constexpr (NAF_DYN) {
+            // m = x a + b per row of this lane, ahead of the statistics (they are those of m)
+            const float *pa = dyn_ma(a, n), *pb = dyn_mb(a, n);
+            float sv[16], tv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                sv[r] = pa[m0 + row_of(r, kk)];
+                tv[r] = pb[m0 + row_of(r, kk)];
+            }
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    xv[tn][r] = __builtin_fmaf(xp[off(r, tn)], sv[r], tv[r]);
+                    psum[tn] += xv[tn][r];
+                }
+        } else {
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
@@ -485,6 +539,7 @@ __global__ __launch_bounds__(2 * C, 2) void naf_head_fwd_kernel(HeadFwdArgs a) {
                 xv[tn][r] = xp[off(r, tn)];
                 psum[tn] += xv[tn][r];
             }
+        }
     }
     float mean[2], rstd[2];
 #pragma unroll
@@ -972,7 +1027,9 @@ static int naf_head_fwd_launch(const TdrNafHeadFwdDesc* d, void* stream) {
 // The forward-only instantiations are a translation unit of their own (tdr_nafblock_infer.hip includes this file with TDR_NAF_INFER_TU
 // defined), so that this file's object holds the training kernels and nothing else.  Compiled in one unit the training kernels come
 // out the same and the forward-only ones do not (profiles/probe_infer_isa.py); the ones tested and measured are the separate unit's.
-#ifdef TDR_NAF_INFER_TU
+// The modulated forward-only chains likewise (tdr_dyn_infer.hip, TDR_NAF_DYN_TU; its entry points follow its #include of this file).
+#if defined(TDR_NAF_DYN_TU)
+#elif defined(TDR_NAF_INFER_TU)
 extern "C" int tdr_naf_tail_infer(const TdrNafTailDesc* d, void* stream) { return naf_tail_fwd_launch<false>(d, stream); }
 extern "C" int tdr_naf_head_infer(const TdrNafHeadFwdDesc* d, void* stream) { return naf_head_fwd_launch<false>(d, stream); }
 #else
@@ -1036,4 +1093,4 @@ extern "C" int tdr_naf_head_bwd(const TdrNafHeadBwdDesc* d, void* stream) {
     if (!d->gw) return TDR_OK;
     return tdr_pair_sum_partials(d->ws, d->N * (d->HW / NPX), d->C, d->gw, d->gb, d->ws + (long)d->N * (d->HW / NPX) * 2 * d->C, stream);
 }
-#endif  // !TDR_NAF_INFER_TU
+#endif  // neither TDR_NAF_DYN_TU nor TDR_NAF_INFER_TU

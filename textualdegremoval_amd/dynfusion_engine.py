@@ -11,6 +11,10 @@ All projections of the network run as ONE launch (csrc/tdr_dynfusion.hip, tdr_kv
 read their slices.  The blocks run the per-op launches of engine.naf_fwd / naf_bwd (the fused head / tail chains are not extended)
 plus the modulation kernels.  sg2's gate is materialised (`h`) and conv5 runs ungated on it.  No ATen arithmetic runs on
 the device: torch only allocates and views memory.
+
+A forward pass no backward follows (keep=False: inference, validation) saves nothing, and where the fused chains are supported a block
+is three launches + SCA (csrc/tdr_dyn_infer.hip: the forward-only head / stencil / tail with the three affines applied in registers,
+DESIGN 5n).
 """
 import torch
 
@@ -20,6 +24,9 @@ from . import leaves as L
 from .kernels import PACK_DGRAD_S1, PACK_FWD
 
 KV_DIM = 10 * 1024          # in_features of every projection (`nn.Linear(10 * 1024, ., bias=False)`, :257, :305)
+# keep=False runs the fused forward-only launches where they are supported; False: the per-op launches everywhere, their intermediates
+# dropped as they go (the A/B of profiles/probe_dynfusion_infer.py, and the same bits as keep=True).  A module switch, no environment knob.
+INFER_KERNELS = True
 
 
 def block_prefixes(cfg):
@@ -102,24 +109,63 @@ def _slices(Kt, off, c):
             Kt[:, off + 6 * c:off + 8 * c], Kt[:, off + 8 * c:off + 10 * c])
 
 
-def dyn_naf_fwd(x, P, Kt, off):
-    """NAFBlock_DynamicFusion.forward (:350-375) on x [N,c,H,W] with the block's projection slices of Kt"""
+def _dyn_naf_infer(x, P, Kt, off):
+    """the block in three fused forward-only launches + SCA (csrc/tdr_dyn_infer.hip); the caller has checked the shape"""
+    c = x.shape[1]
+    a0, b0, a1, b1, a2, b2 = _slices(Kt, off, c)
+    w1p, w3p, w4p, w5p = (K.pack_weights(P[k], PACK_FWD)[0] for k in ('conv1.weight', 'conv3.weight', 'conv4.weight', 'conv5.weight'))
+    t1 = K.dyn_head_infer(x, a0, b0, P['norm1.weight'], P['norm1.bias'], E.LN_EPS, w1p, P['conv1.bias'])
+    g, pooled = K.dyn_dwsg_fwd(t1, P['conv2.weight'], P['conv2.bias'], a1, b1)
+    t1 = None
+    s = K.sca_fwd(pooled, P['sca.1.weight'], P['sca.1.bias'])
+    return K.dyn_tail_infer(g, s, x, w3p, P['conv3.bias'], P['beta'].view(-1), P['norm2.weight'], P['norm2.bias'], E.LN_EPS, w4p,
+                            P['conv4.bias'], a2, b2, w5p, P['conv5.bias'], P['gamma'].view(-1))
+
+
+def infer_fused_ok(x):
+    """the support of the fused forward-only block: that of the NAFBlock chains (c in {32, 64, 128, 256}, HW % 64 == 0, a split
+    arithmetic), rows the stencil reads as float4, a dense input"""
     N, c, H, W = x.shape
+    return K.naf_tail_supported(c, H * W) and W % 4 == 0 and N <= 16 and x.is_contiguous()
+
+
+def dyn_naf_fwd(x, P, Kt, off, keep=True):
+    """NAFBlock_DynamicFusion.forward (:350-375) on x [N,c,H,W] with the block's projection slices of Kt.
+    keep=False: a forward pass no backward follows -> (out, None).  Supported shapes run three fused launches + SCA (INFER_KERNELS);
+    every other shape runs the same per-op launches as keep=True (same bits) and drops each intermediate once its last consumer is
+    enqueued, as engine.naf_fwd does."""
+    N, c, H, W = x.shape
+    if not keep and INFER_KERNELS and infer_fused_ok(x):
+        return _dyn_naf_infer(x, P, Kt, off), None
     a0, b0, a1, b1, a2, b2 = _slices(Kt, off, c)
     xn, mu1, rs1 = K.modln_fwd(x, a0, b0, P['norm1.weight'], P['norm1.bias'], E.LN_EPS)
     wp, mp, *_ = K.pack_weights(P['conv1.weight'], PACK_FWD)
     t1 = K.conv_forward(xn, wp, mp, 2 * c, 1, bias=P['conv1.bias'])
+    if not keep:
+        xn = mu1 = rs1 = None
     d2 = K.dwk_fwd(t1, P['conv2.weight'], P['conv2.bias'])
+    if not keep:
+        t1 = None
     g, pooled = K.modgate_fwd(d2, a1, b1, want_pool=True)
+    if not keep:
+        d2 = None
     s = K.sca_fwd(pooled, P['sca.1.weight'], P['sca.1.bias'])
     wp, mp, *_ = K.pack_weights(P['conv3.weight'], PACK_FWD)
     y = K.conv_forward(g, wp, mp, c, 1, kscale=s, bias=P['conv3.bias'], scale=P['beta'].view(-1), res=x)
+    if not keep:
+        g = None
     yn, mu2, rs2 = K.layernorm2d_fwd(y, P['norm2.weight'], P['norm2.bias'], E.LN_EPS)
     wp, mp, *_ = K.pack_weights(P['conv4.weight'], PACK_FWD)
     t4 = K.conv_forward(yn, wp, mp, 2 * c, 1, bias=P['conv4.bias'])
+    if not keep:
+        yn = mu2 = rs2 = None
     h, _ = K.modgate_fwd(t4, a2, b2)
+    if not keep:
+        t4 = None
     wp, mp, *_ = K.pack_weights(P['conv5.weight'], PACK_FWD)
     out = K.conv_forward(h, wp, mp, c, 1, bias=P['conv5.bias'], scale=P['gamma'].view(-1), res=y)
+    if not keep:
+        return out, None
     return out, (x, xn, mu1, rs1, t1, d2, g, pooled, s, y, yn, mu2, rs2, t4, h, off)
 
 
@@ -166,13 +212,13 @@ def dyn_naf_bwd(dout, P, saved, Kt, dK):
     return dx, G
 
 
-def _seq_fwd(x, P, pre, n, Kt, tab):
+def _seq_fwd(x, P, pre, n, Kt, tab, keep=True):
     saved = []
     for i in range(n):
         bp = f'{pre}{i}.'
-        x, sv = dyn_naf_fwd(x, E._sub(P, bp), Kt, tab.offs[bp])
+        x, sv = dyn_naf_fwd(x, E._sub(P, bp), Kt, tab.offs[bp], keep=keep)
         saved.append(sv)
-    return x, saved
+    return x, (saved if keep else None)
 
 
 def _seq_bwd(d, P, pre, n, saved, Kt, dK, G):
@@ -198,13 +244,24 @@ def flat_kv(kv, N):
     return kvf.contiguous()
 
 
-def dyn_unet_fwd(P, cfg, inp, kv):
+def dyn_unet_fwd(P, cfg, inp, kv, keep=True):
     """NAFNetDynamicFusion.forward (:512-536) -> (out, saved): engine.walk_fwd over the modulated blocks; saved = the walk's
-    + (kvf, Kt, projection table)"""
+    + (kvf, Kt, projection table).  keep=False: (out, None) -- the walk releases the skips behind their decoder level, the blocks save
+    nothing (dyn_naf_fwd)."""
     kvf = flat_kv(kv, inp.shape[0])
     tab, Kt = proj_fwd(P, block_prefixes(cfg), kvf)
-    out, saved = E.walk_fwd(P, cfg, inp, seq=lambda x, P, pre, n: _seq_fwd(x, P, pre + 'layers.', n, Kt, tab))
-    return out, saved + (kvf, Kt, tab)
+    out, saved = E.walk_fwd(P, cfg, inp, seq=lambda x, P, pre, n, keep=True: _seq_fwd(x, P, pre + 'layers.', n, Kt, tab, keep=keep),
+                            keep=keep)
+    return out, (saved + (kvf, Kt, tab) if keep else None)
+
+
+def dyn_block_fwd(P, cfg, x, kv, keep=True):
+    """one NAFBlock_DynamicFusion with its own projection table (the module on its own) -> (out, saved); saved = (block's, table, kvf, Kt).
+    cfg is unused (the signature of the whole-network forwards)"""
+    kvf = flat_kv(kv, x.shape[0])
+    tab, Kt = proj_fwd(P, [('', x.shape[1])], kvf)
+    out, saved = dyn_naf_fwd(x.contiguous(), P, Kt, 0, keep=keep)
+    return out, ((saved, tab, kvf, Kt) if keep else None)
 
 
 def dyn_unet_bwd(dout, P, cfg, saved, need_dkv=True, G=None):

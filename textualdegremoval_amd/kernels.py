@@ -2527,3 +2527,57 @@ def modgate_bwd(dg, t, a, b, da, db, dg_bias=None, dg_bias_mul=1.0):
     check(_lib.load().tdr_modgate_bwd(dg.data_ptr(), _p(dg_bias), float(dg_bias_mul), t.data_ptr(), pa, pb, ns, N, c, H * W, dt.data_ptr(),
                                       pda, pdb, dns, _stream()), 'tdr_modgate_bwd')
     return dt
+
+
+# ---- NAFBlock_DynamicFusion for a pass that keeps nothing: three launches per block (csrc/tdr_dyn_infer.hip)
+def dyn_head_infer(x, a0, b0, lnw, lnb, eps, w1p, b1):
+    """t1 = conv1(LayerNorm2d(x a0 + b0)) (a0, b0: [N, c] row slices); the modulated input, xn, mu and rs are not written"""
+    N, Cc, H, W = x.shape
+    (pa, ns), (pb, nsb) = _rowvec(a0), _rowvec(b0)
+    assert ns == nsb
+    t1 = torch.empty(N, 2 * Cc, H, W, dtype=torch.float32, device=x.device)
+    d = _lib.TdrDynHeadDesc()
+    d.N, d.C, d.HW, d.w_fmt = N, Cc, H * W, w1p.fmt
+    d.x, d.x_ns, d.a0, d.b0, d.ab_ns = x.data_ptr(), _dense_nchw(x), pa, pb, ns
+    d.lnw, d.lnb, d.eps = lnw.data_ptr(), lnb.data_ptr(), float(eps)
+    d.w1, d.b1, d.t1, d.t1_ns = w1p.data_ptr(), b1.data_ptr(), t1.data_ptr(), _dense_nchw(t1)
+    check(_lib.load().tdr_dyn_head_infer(C.byref(d), _stream()), 'tdr_dyn_head_infer')
+    return t1
+
+
+def dyn_dwsg_fwd(t, w, b, a1, b1):
+    """t [N, 2c, H, W]: u = (dw3x3(t) + b) a1 + b1 (a1, b1: [N, 2c] row slices), g = u[:c] u[c:] -> (g, pooled [N, c] = mean g);
+    the depthwise output is not written"""
+    lib = _lib.load()
+    N, C2, H, W = t.shape
+    Cc = C2 // 2
+    assert t.is_contiguous()
+    (pa, ns), (pb, nsb) = _rowvec(a1), _rowvec(b1)
+    assert ns == nsb
+    g = torch.empty(N, Cc, H, W, dtype=torch.float32, device=t.device)
+    pooled = torch.empty(N, Cc, dtype=torch.float32, device=t.device)
+    ws = workspace(lib.tdr_dyn_dwsg_ws_floats(N, Cc, H, W), t.device)
+    d = _lib.TdrDynDwsgDesc()
+    d.N, d.C, d.H, d.W = N, Cc, H, W
+    d.t, d.w, d.b, d.a1, d.b1, d.ab_ns = t.data_ptr(), w.data_ptr(), b.data_ptr(), pa, pb, ns
+    d.g, d.pooled, d.ws = g.data_ptr(), pooled.data_ptr(), ws.data_ptr()
+    check(lib.tdr_dyn_dwsg_fwd(C.byref(d), _stream()), 'tdr_dyn_dwsg_fwd')
+    return g, pooled
+
+
+def dyn_tail_infer(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, a2, b2, w5p, b5, gamma):
+    """naf_tail_infer with conv4's output times a2 plus b2 (a2, b2: [N, 2c] row slices) ahead of the SimpleGate -> out alone"""
+    N, Cc, H, W = g.shape
+    (pa, ns), (pb, nsb) = _rowvec(a2), _rowvec(b2)
+    assert ns == nsb and w3p.fmt == w4p.fmt == w5p.fmt
+    out = torch.empty(N, Cc, H, W, dtype=torch.float32, device=g.device)
+    d = _lib.TdrDynTailDesc()
+    d.N, d.C, d.HW, d.w_fmt, d.eps = N, Cc, H * W, w3p.fmt, float(eps)
+    d.g, d.g_ns, d.sca, d.x, d.x_ns = g.data_ptr(), _dense_nchw(g), s.data_ptr(), x.data_ptr(), _dense_nchw(x)
+    d.w3, d.w4, d.w5 = w3p.data_ptr(), w4p.data_ptr(), w5p.data_ptr()
+    d.b3, d.beta, d.lnw, d.lnb = b3.data_ptr(), beta.data_ptr(), lnw.data_ptr(), lnb.data_ptr()
+    d.b4, d.b5, d.gamma = b4.data_ptr(), b5.data_ptr(), gamma.data_ptr()
+    d.a2, d.b2, d.ab_ns = pa, pb, ns
+    d.out, d.out_ns = out.data_ptr(), _dense_nchw(out)
+    check(_lib.load().tdr_dyn_tail_infer(C.byref(d), _stream()), 'tdr_dyn_tail_infer')
+    return out

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from ... import dynfusion_engine as D
 from ... import leaves as L
-from .nafnet_arch_utils import LayerNorm2d, require_gpu
+from .nafnet_arch_utils import LayerNorm2d, infer_fwd as _infer_fwd, require_gpu
 from .network_nafnet_guided_arch import NAFBlock, NAFNet, NAFNetLocal, SimpleGate, _named  # noqa: F401
 
 
@@ -100,7 +100,8 @@ class NAFBlock_DynamicFusion(nn.Module):
 
     def forward(self, inp, k_v):
         names, params = _named(self)
-        return _DynBlockFn.apply(inp, k_v, names, *params)
+        out = _infer_fwd('NAFBlock_DynamicFusion', D.dyn_block_fwd, names, params, None, inp, k_v)
+        return out if out is not None else _DynBlockFn.apply(inp, k_v, names, *params)
 
 
 class DynamicBasicLayer(nn.Module):
@@ -151,7 +152,8 @@ class NAFNetDynamicFusion(nn.Module):
     def forward(self, inp, k_v):
         D.flat_kv(k_v, inp.shape[0])          # (shape checks first: a 20-word embedding fails as in the reference, defect R10)
         names, params = _named(self)
-        return _DynNetFn.apply(inp, k_v, names, self.cfg, *params)
+        out = _infer_fwd('NAFNetDynamicFusion', D.dyn_unet_fwd, names, params, self.cfg, inp, k_v)
+        return out if out is not None else _DynNetFn.apply(inp, k_v, names, self.cfg, *params)
 
 
 class NAFNetLocalDynamic(NAFNetDynamicFusion):
