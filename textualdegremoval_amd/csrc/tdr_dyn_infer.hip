@@ -1,14 +1,14 @@
 // Forward-only NAFBlock_DynamicFusion in three launches (models/archs/network_nafnet_guided_diffir_arch.py:350-375, inference):
-//   tdr_dyn_head_infer   t1  = conv1(norm1(x a0 + b0))                               naf_head_fwd_kernel<C, false, SCH>, modulated
+//   tdr_dyn_head_infer   t1  = conv1(norm1(x a0 + b0))                               naf_head_fwd_kernel<C, false, SCH, MOD = true>
 //   tdr_dyn_dwsg_fwd     g   = u[:c] u[c:], u = (dw3x3(t1) + bias) a1 + b1 ; SCA pool partials of g            (stencil, below)
 //   tdr_dyn_tail_infer   out = conv3 -> beta residual -> norm2 -> conv4 -> (. a2 + b2) -> gate -> conv5 -> gamma residual
-//                                                                                    naf_tail_fwd_kernel<C, false, SCH>, modulated
+//                                                                                    naf_tail_fwd_kernel<C, false, SCH, MOD = true>
 // a*, b*: per-(image, channel) rows of the projection output (dynfusion_engine.ProjTable).  Nothing a backward pass would read is
 // written: xn, mu, rs, d2, y, yn, t4 and the gate h stay on the chip.
-// The chains are tdr_nafblock.hip compiled with TDR_NAF_DYN_TU (a translation unit of its own, like tdr_nafblock_infer.hip: the objects
-// of the training and the un-modulated forward-only kernels hold what they held).
-#define TDR_NAF_DYN_TU 1
-#include "tdr_nafblock.hip"
+// The chains are the MOD = true instantiations of the kernels in tdr_nafblock_chain.h, in a translation unit of their own like the plain
+// forward-only ones (tdr_nafblock_infer.hip); the row access, geometry and pool finish of the stencil are tdr_dw_stencil.h.
+#include "tdr_nafblock_chain.h"
+#include "tdr_dw_stencil.h"
 
 namespace {
 
@@ -34,23 +34,6 @@ struct DynDwArgs {
     int C, H, W, tprw_log2, rpt, ncb;
     float pscale;
 };
-
-struct DynRow6 { float v[6]; };
-
-// one row of the 4-column strip with its two horizontal neighbours; zero outside the image
-__device__ __forceinline__ DynRow6 dyn_fetch_row(const float* __restrict__ plane, int y, int x0, int H, int W, bool active, bool left_lane,
-                                                 bool right_lane) {
-    const bool rok = active && y >= 0 && y < H;
-    const float* row = plane + (long)min(max(y, 0), H - 1) * W;
-    f32x4 m = {0.f, 0.f, 0.f, 0.f};
-    if (rok) m = *reinterpret_cast<const f32x4*>(row + x0);
-    float l = __shfl_up(m[3], 1, 64), r = __shfl_down(m[0], 1, 64);
-    if (!left_lane) l = (rok && x0 > 0) ? row[x0 - 1] : 0.f;
-    if (!right_lane) r = (rok && x0 + 4 < W) ? row[x0 + 4] : 0.f;
-    DynRow6 o;
-    o.v[0] = l; o.v[1] = m[0]; o.v[2] = m[1]; o.v[3] = m[2]; o.v[4] = m[3]; o.v[5] = r;
-    return o;
-}
 
 __global__ __launch_bounds__(256) void dyn_dwsg_fwd_kernel(DynDwArgs a) {
     __shared__ float red[4];
@@ -79,15 +62,15 @@ __global__ __launch_bounds__(256) void dyn_dwsg_fwd_kernel(DynDwArgs a) {
     const float t1 = a.mb[(long)n * a.m_ns + c], t2 = a.mb[(long)n * a.m_ns + c + C];
     float acc = 0.f;
 
-    DynRow6 r1[3], r2[3];
-    r1[0] = dyn_fetch_row(p1, ybeg - 1, x0, H, W, active, left_lane, right_lane);
-    r2[0] = dyn_fetch_row(p2, ybeg - 1, x0, H, W, active, left_lane, right_lane);
-    r1[1] = dyn_fetch_row(p1, ybeg, x0, H, W, active, left_lane, right_lane);
-    r2[1] = dyn_fetch_row(p2, ybeg, x0, H, W, active, left_lane, right_lane);
+    Row6 r1[3], r2[3];
+    r1[0] = fetch_row(p1, ybeg - 1, x0, H, W, active, left_lane, right_lane);
+    r2[0] = fetch_row(p2, ybeg - 1, x0, H, W, active, left_lane, right_lane);
+    r1[1] = fetch_row(p1, ybeg, x0, H, W, active, left_lane, right_lane);
+    r2[1] = fetch_row(p2, ybeg, x0, H, W, active, left_lane, right_lane);
     for (int i = 0; i < a.rpt; ++i) {
         const int y = ybeg + i;
-        r1[2] = dyn_fetch_row(p1, y + 1, x0, H, W, active, left_lane, right_lane);     // uniform trip count: shuffles stay converged
-        r2[2] = dyn_fetch_row(p2, y + 1, x0, H, W, active, left_lane, right_lane);
+        r1[2] = fetch_row(p1, y + 1, x0, H, W, active, left_lane, right_lane);     // uniform trip count: shuffles stay converged
+        r2[2] = fetch_row(p2, y + 1, x0, H, W, active, left_lane, right_lane);
         float o1[4] = {b1, b1, b1, b1}, o2[4] = {b2, b2, b2, b2};
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
@@ -114,48 +97,17 @@ __global__ __launch_bounds__(256) void dyn_dwsg_fwd_kernel(DynDwArgs a) {
     if (tid == 0) a.part[((long)n * C + c) * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * a.pscale;
 }
 
-// the fixed-order finish of the pool partials (dw_pool_finish_kernel of tdr_dwsg.hip)
-__global__ void dyn_pool_finish_kernel(const float* __restrict__ part, int NC, int nb, float inv_hw, float* __restrict__ pooled) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= NC) return;
-    float s = 0.f;
-    for (int k = 0; k < nb; ++k) s += part[(long)i * nb + k];
-    pooled[i] = s * inv_hw;
-}
-
-struct DynDwGeom { int tprw_log2, rpt, ncb, nby, nb; };
-
-// the launch geometry of tdr_dwsg_fwd (dw_geom of tdr_dwsg.hip)
-DynDwGeom dyn_dw_geom(int H, int W) {
-    DynDwGeom g;
-    int groups = W / 4, lg = 0;
-    while ((1 << lg) < groups && lg < 8) ++lg;          // threads per row block: next power of two, at most 256
-    g.tprw_log2 = lg;
-    const int spb = 256 >> lg;                           // strips per block
-    g.ncb = tdr_cdiv(groups, 1 << lg);
-    int rpt = tdr_cdiv(H, spb);                          // rows per thread: up to 8, fewer on small maps (more blocks)
-    if (rpt > 8) rpt = 8;
-    if (rpt < 1) rpt = 1;
-    g.rpt = rpt;
-    g.nby = tdr_cdiv(H, spb * rpt);
-    g.nb = g.ncb * g.nby;
-    return g;
-}
-
 }  // namespace
 
 extern "C" int tdr_dyn_head_infer(const TdrDynHeadDesc* d, void* stream) {
     const char* fn = "tdr_dyn_head_infer";
     TDR_REQUIRE(d && d->x && d->a0 && d->b0 && d->lnw && d->lnb && d->w1 && d->b1 && d->t1, "%s: null pointer", fn);
     if (int rc = dyn_check_common(fn, d->N, d->C, d->HW, d->w_fmt)) return rc;
-    HeadFwdArgs a;
-    a.x = d->x; a.x_ns = d->x_ns; a.lnw = d->lnw; a.lnb = d->lnb; a.eps = d->eps;
-    a.w1 = reinterpret_cast<const uint4*>(d->w1); a.b1 = d->b1;
-    a.mu = nullptr; a.rs = nullptr; a.xn = nullptr; a.xn_ns = 0; a.t1 = d->t1; a.t1_ns = d->t1_ns; a.HW = d->HW;
+    HeadFwdArgs<true> a;
+    naf_head_fill(a, d);
     a.ma = d->a0; a.mb = d->b0; a.m_ns = d->ab_ns;
     const bool bx = d->w_fmt == 1;
-    const size_t lds = (size_t)(bx ? 3 : 2) * (d->C / 8) * NPX * 16 + (size_t)2 * (d->C / 32) * NPX * sizeof(float);      // planes + red[2][C / 32 waves][64 px]
-    NAF_DISPATCH_CS(naf_head_fwd_kernel, NAF_COMMA false, lds, a, d, stream);
+    NAF_DISPATCH_CS(naf_head_fwd_kernel, NAF_COMMA false, NAF_COMMA true, naf_fwd_lds_bytes(d->C, bx), a, d, stream);
     TDR_LAUNCH_CHECK("naf_head_fwd_kernel<dyn infer>");
     return TDR_OK;
 }
@@ -167,24 +119,17 @@ extern "C" int tdr_dyn_tail_infer(const TdrDynTailDesc* d, void* stream) {
                 "%s: null pointer", fn);
     if (int rc = dyn_check_common(fn, d->N, d->C, d->HW, d->w_fmt)) return rc;
     TDR_REQUIRE(d->g_ns % 4 == 0 && (reinterpret_cast<uintptr_t>(d->g) & 15) == 0, "%s: g must be 16-byte aligned", fn);
-    TailArgs a;
-    a.g = d->g; a.g_ns = d->g_ns; a.sca = d->sca; a.x = d->x; a.x_ns = d->x_ns;
-    a.w3 = reinterpret_cast<const uint4*>(d->w3); a.w4 = reinterpret_cast<const uint4*>(d->w4); a.w5 = reinterpret_cast<const uint4*>(d->w5);
-    a.b3 = d->b3; a.beta = d->beta; a.lnw = d->lnw; a.lnb = d->lnb; a.b4 = d->b4; a.b5 = d->b5; a.gamma = d->gamma;
-    a.eps = d->eps;
-    a.y = nullptr; a.y_ns = 0; a.mu = nullptr; a.rs = nullptr; a.yn = nullptr; a.yn_ns = 0; a.t4 = nullptr; a.t4_ns = 0;
-    a.out = d->out; a.out_ns = d->out_ns; a.HW = d->HW;
-    a.c_out = d->C;
+    TailArgs<true> a;
+    naf_tail_fill(a, d);
     a.ma = d->a2; a.mb = d->b2; a.m_ns = d->ab_ns;
     const bool bx = d->w_fmt == 1;
-    const size_t lds = (size_t)(bx ? 3 : 2) * (d->C / 8) * NPX * 16 + (size_t)2 * (d->C / 32) * NPX * sizeof(float);      // planes + red[2][C / 32 waves][64 px]
-    NAF_DISPATCH_CS(naf_tail_fwd_kernel, NAF_COMMA false, lds, a, d, stream);
+    NAF_DISPATCH_CS(naf_tail_fwd_kernel, NAF_COMMA false, NAF_COMMA true, naf_fwd_lds_bytes(d->C, bx), a, d, stream);
     TDR_LAUNCH_CHECK("naf_tail_fwd_kernel<dyn infer>");
     return TDR_OK;
 }
 
 extern "C" int64_t tdr_dyn_dwsg_ws_floats(int N, int C, int H, int W) {
-    return (int64_t)N * C * dyn_dw_geom(H, W).nb;
+    return (int64_t)N * C * dw_geom(H, W).nb;
 }
 
 extern "C" int tdr_dyn_dwsg_fwd(const TdrDynDwsgDesc* d, void* stream) {
@@ -197,14 +142,14 @@ extern "C" int tdr_dyn_dwsg_fwd(const TdrDynDwsgDesc* d, void* stream) {
     TDR_REQUIRE((reinterpret_cast<uintptr_t>(d->t) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->g) & 15) == 0,
                 "%s: t and g must be 16-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
-    const DynDwGeom q = dyn_dw_geom(d->H, d->W);
+    const DwGeom q = dw_geom(d->H, d->W);
     const float inv_hw = 1.0f / (float)((long)d->H * d->W);
     const bool one = q.nb == 1;      // one block per plane: the partial IS the pool sum -- no finish launch
     DynDwArgs a{d->t, d->w, d->b, d->a1, d->b1, (long)d->ab_ns, d->g, one ? d->pooled : d->ws, d->C, d->H, d->W, q.tprw_log2, q.rpt, q.ncb,
                 one ? inv_hw : 1.0f};
     hipLaunchKernelGGL(dyn_dwsg_fwd_kernel, dim3(q.nb, d->C, d->N), dim3(256), 0, st, a);
     if (!one)
-        hipLaunchKernelGGL(dyn_pool_finish_kernel, dim3(tdr_cdiv(d->N * d->C, 256)), dim3(256), 0, st, d->ws, d->N * d->C, q.nb, inv_hw,
+        hipLaunchKernelGGL(dw_pool_finish_kernel, dim3(tdr_cdiv(d->N * d->C, 256)), dim3(256), 0, st, d->ws, d->N * d->C, q.nb, inv_hw,
                            d->pooled);
     TDR_LAUNCH_CHECK("dyn_dwsg_fwd");
     return TDR_OK;

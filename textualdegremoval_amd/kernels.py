@@ -935,15 +935,18 @@ def dwsg_bwd(dg, t, w, b, dg_bias=None, dg_bias_mul=1.0, defer_finish=False):
 
 def naf_tail_supported(c, hw, c_out=None):
     ok_out = c_out is None or c_out == c or (2 * c_out == c and c_out % 32 == 0)
-    # 'hx2': fp16 pair planes in LDS (loss-scaled backward); 'bx3': bf16 triple planes, fp32 range (csrc/tdr_nafblock.hip, SchT)
+    # 'hx2': fp16 pair planes in LDS (loss-scaled backward); 'bx3': bf16 triple planes, fp32 range (csrc/tdr_nafblock_chain.h, SchT)
     return ok_out and MATH in ('hx2', 'bx3') and bool(_lib.load().tdr_naf_tail_supported(int(c), int(hw)))
 
 
-def _naf_tail_desc(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out):
-    """descriptor of tdr_naf_tail_fwd / tdr_naf_tail_infer without the saved tensors (NULL: what the forward-only chain wants)"""
+def _naf_tail_desc(cls, g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out):
+    """descriptor `cls` (TdrNafTailDesc: tdr_naf_tail_fwd / tdr_naf_tail_infer; TdrDynTailDesc, which has no c_out: tdr_dyn_tail_infer)
+    without the saved tensors (NULL: what the forward-only chains want) and without the modulation rows"""
     N, Cc, H, W = g.shape
-    d = _lib.TdrNafTailDesc()
-    d.N, d.C, d.HW, d.eps, d.c_out = N, Cc, H * W, float(eps), c_out
+    d = cls()
+    d.N, d.C, d.HW, d.eps = N, Cc, H * W, float(eps)
+    if c_out is not None:
+        d.c_out = c_out
     assert w3p.fmt == w4p.fmt == w5p.fmt
     d.w_fmt = w3p.fmt
     d.g, d.g_ns, d.sca, d.x, d.x_ns = g.data_ptr(), _dense_nchw(g), s.data_ptr(), x.data_ptr(), _dense_nchw(x)
@@ -967,7 +970,7 @@ def naf_tail_fwd(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma,
     t4 = torch.empty(N, 2 * Cc, H, W, dtype=torch.float32, device=dev)
     mu = torch.empty(N, H * W, dtype=torch.float32, device=dev)
     rs = torch.empty_like(mu)
-    d = _naf_tail_desc(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out)
+    d = _naf_tail_desc(_lib.TdrNafTailDesc, g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out)
     d.y, d.y_ns, d.mu, d.rs, d.yn, d.yn_ns = y.data_ptr(), _dense_nchw(y), mu.data_ptr(), rs.data_ptr(), yn.data_ptr(), _dense_nchw(yn)
     d.t4, d.t4_ns = t4.data_ptr(), _dense_nchw(t4)
     if _survey is not None:
@@ -985,7 +988,7 @@ def naf_tail_infer(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamm
     N, Cc, H, W = g.shape
     c_out = Cc if c_out is None else c_out
     out = torch.empty(N, c_out, H, W, dtype=torch.float32, device=g.device)
-    d = _naf_tail_desc(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out)
+    d = _naf_tail_desc(_lib.TdrNafTailDesc, g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, c_out, out)
     check(_lib.load().tdr_naf_tail_infer(C.byref(d), _stream()), 'tdr_naf_tail_infer')
     return out
 
@@ -1048,6 +1051,17 @@ def naf_tail_bwd(dout, gamma, t4, y, mu, rs, lnw, w5tp, w4tp, w3tp=None, beta=No
     return (dy, dt4, gw, gb) if dgp is None else (dy, dt4, gw, gb, dgp)
 
 
+def _naf_head_desc(cls, x, lnw, lnb, eps, w1p, b1, t1):
+    """descriptor `cls` (TdrNafHeadFwdDesc: tdr_naf_head_fwd / tdr_naf_head_infer; TdrDynHeadDesc: tdr_dyn_head_infer) without the saved
+    tensors (NULL: what the forward-only chains want) and without the modulation rows"""
+    N, Cc, H, W = x.shape
+    d = cls()
+    d.N, d.C, d.HW, d.w_fmt = N, Cc, H * W, w1p.fmt
+    d.x, d.x_ns, d.lnw, d.lnb, d.eps = x.data_ptr(), _dense_nchw(x), lnw.data_ptr(), lnb.data_ptr(), float(eps)
+    d.w1, d.b1, d.t1, d.t1_ns = w1p.data_ptr(), b1.data_ptr(), t1.data_ptr(), _dense_nchw(t1)
+    return d
+
+
 def naf_head_fwd(x, lnw, lnb, eps, w1p, b1):
     """fused norm1 -> conv1.  Returns (xn, mu, rs, t1)."""
     lib = _lib.load()
@@ -1057,11 +1071,8 @@ def naf_head_fwd(x, lnw, lnb, eps, w1p, b1):
     t1 = torch.empty(N, 2 * Cc, H, W, dtype=torch.float32, device=dev)
     mu = torch.empty(N, H * W, dtype=torch.float32, device=dev)
     rs = torch.empty_like(mu)
-    d = _lib.TdrNafHeadFwdDesc()
-    d.N, d.C, d.HW, d.w_fmt = N, Cc, H * W, w1p.fmt
-    d.x, d.x_ns, d.lnw, d.lnb, d.eps = x.data_ptr(), _dense_nchw(x), lnw.data_ptr(), lnb.data_ptr(), float(eps)
-    d.w1, d.b1 = w1p.data_ptr(), b1.data_ptr()
-    d.mu, d.rs, d.xn, d.xn_ns, d.t1, d.t1_ns = mu.data_ptr(), rs.data_ptr(), xn.data_ptr(), _dense_nchw(xn), t1.data_ptr(), _dense_nchw(t1)
+    d = _naf_head_desc(_lib.TdrNafHeadFwdDesc, x, lnw, lnb, eps, w1p, b1, t1)
+    d.mu, d.rs, d.xn, d.xn_ns = mu.data_ptr(), rs.data_ptr(), xn.data_ptr(), _dense_nchw(xn)
     if _survey is not None:
         _survey.probe(x, 'fwd')
     check(lib.tdr_naf_head_fwd(C.byref(d), _stream()), 'tdr_naf_head_fwd')
@@ -1072,10 +1083,7 @@ def naf_head_infer(x, lnw, lnb, eps, w1p, b1):
     """norm1 -> conv1 for a pass that keeps nothing: -> t1 alone, bit-identical to naf_head_fwd's (xn, mu, rs are not written)"""
     N, Cc, H, W = x.shape
     t1 = torch.empty(N, 2 * Cc, H, W, dtype=torch.float32, device=x.device)
-    d = _lib.TdrNafHeadFwdDesc()
-    d.N, d.C, d.HW, d.w_fmt = N, Cc, H * W, w1p.fmt
-    d.x, d.x_ns, d.lnw, d.lnb, d.eps = x.data_ptr(), _dense_nchw(x), lnw.data_ptr(), lnb.data_ptr(), float(eps)
-    d.w1, d.b1, d.t1, d.t1_ns = w1p.data_ptr(), b1.data_ptr(), t1.data_ptr(), _dense_nchw(t1)
+    d = _naf_head_desc(_lib.TdrNafHeadFwdDesc, x, lnw, lnb, eps, w1p, b1, t1)
     check(_lib.load().tdr_naf_head_infer(C.byref(d), _stream()), 'tdr_naf_head_infer')
     return t1
 
@@ -2536,11 +2544,8 @@ def dyn_head_infer(x, a0, b0, lnw, lnb, eps, w1p, b1):
     (pa, ns), (pb, nsb) = _rowvec(a0), _rowvec(b0)
     assert ns == nsb
     t1 = torch.empty(N, 2 * Cc, H, W, dtype=torch.float32, device=x.device)
-    d = _lib.TdrDynHeadDesc()
-    d.N, d.C, d.HW, d.w_fmt = N, Cc, H * W, w1p.fmt
-    d.x, d.x_ns, d.a0, d.b0, d.ab_ns = x.data_ptr(), _dense_nchw(x), pa, pb, ns
-    d.lnw, d.lnb, d.eps = lnw.data_ptr(), lnb.data_ptr(), float(eps)
-    d.w1, d.b1, d.t1, d.t1_ns = w1p.data_ptr(), b1.data_ptr(), t1.data_ptr(), _dense_nchw(t1)
+    d = _naf_head_desc(_lib.TdrDynHeadDesc, x, lnw, lnb, eps, w1p, b1, t1)
+    d.a0, d.b0, d.ab_ns = pa, pb, ns
     check(_lib.load().tdr_dyn_head_infer(C.byref(d), _stream()), 'tdr_dyn_head_infer')
     return t1
 
@@ -2569,15 +2574,9 @@ def dyn_tail_infer(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, a2, b2, w5p, 
     """naf_tail_infer with conv4's output times a2 plus b2 (a2, b2: [N, 2c] row slices) ahead of the SimpleGate -> out alone"""
     N, Cc, H, W = g.shape
     (pa, ns), (pb, nsb) = _rowvec(a2), _rowvec(b2)
-    assert ns == nsb and w3p.fmt == w4p.fmt == w5p.fmt
+    assert ns == nsb
     out = torch.empty(N, Cc, H, W, dtype=torch.float32, device=g.device)
-    d = _lib.TdrDynTailDesc()
-    d.N, d.C, d.HW, d.w_fmt, d.eps = N, Cc, H * W, w3p.fmt, float(eps)
-    d.g, d.g_ns, d.sca, d.x, d.x_ns = g.data_ptr(), _dense_nchw(g), s.data_ptr(), x.data_ptr(), _dense_nchw(x)
-    d.w3, d.w4, d.w5 = w3p.data_ptr(), w4p.data_ptr(), w5p.data_ptr()
-    d.b3, d.beta, d.lnw, d.lnb = b3.data_ptr(), beta.data_ptr(), lnw.data_ptr(), lnb.data_ptr()
-    d.b4, d.b5, d.gamma = b4.data_ptr(), b5.data_ptr(), gamma.data_ptr()
+    d = _naf_tail_desc(_lib.TdrDynTailDesc, g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma, None, out)
     d.a2, d.b2, d.ab_ns = pa, pb, ns
-    d.out, d.out_ns = out.data_ptr(), _dense_nchw(out)
     check(_lib.load().tdr_dyn_tail_infer(C.byref(d), _stream()), 'tdr_dyn_tail_infer')
     return out
