@@ -22,9 +22,9 @@ extern "C" {
 
 /* C-ABI version: bumped with every incompatible change of this header (100 rounds 1-2, 101 round 3, 102 round 4, 103 - 104
  * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
- * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*); the
+ * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local); the
  * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
-#define TDR_ABI_VERSION 111
+#define TDR_ABI_VERSION 112
 int tdr_version(void);
 const char* tdr_last_error(void);
 
@@ -749,6 +749,24 @@ int tdr_naf_tail_fwd(const TdrNafTailDesc* d, void* stream);
  * strides are ignored).  Same kernel body with those stores compiled out -- tile shape, wave count, MFMA sequence, reduction order
  * and support are tdr_naf_tail_fwd's, so `out` is bit-identical to it in every arithmetic. */
 int tdr_naf_tail_infer(const TdrNafTailDesc* d, void* stream);
+/* The forward-only chain of a NAFBlock under TLSC (`NAFNetLocal`, nafnet_local_arch.py:10-104; csrc/tdr_nafblock_local.hip, ABI 112): the
+ * channel attention is a per-pixel map, s = W_sca pool + b_sca with `pool` the box-mean map of g (tdr_local_avgpool), formed in the
+ * kernel by one more GEMM in front of conv3, whose operand is g * s:
+ *   y = x + conv3(g * (W_sca pool + b_sca)) * beta;  out = y + conv5(SimpleGate(conv4(norm2(y)))) * gamma
+ * Only `out` is written.  TdrNafTailDesc without the saved tensors, c_out (a TLSC block is never a fusion block) and the sca row;
+ * wsca: the sca conv (C x C) packed like w3 (mode FWD, same w_fmt).  Tile, waves, LDS and support are tdr_naf_tail_infer's;
+ * pool must be 16-byte aligned (pool_ns % 4 == 0). */
+typedef struct TdrNafTailLocalDesc {
+    int N, C, HW, w_fmt;
+    float eps;
+    const float* g;    int64_t g_ns;         /* [N, C, HW] SimpleGate output of the first half */
+    const float* pool; int64_t pool_ns;      /* [N, C, HW] box mean of g */
+    const float* x;    int64_t x_ns;         /* block input (residual) */
+    const void *wsca, *w3, *w4, *w5;
+    const float *bsca, *b3, *beta, *lnw, *lnb, *b4, *b5, *gamma;
+    float* out; int64_t out_ns;
+} TdrNafTailLocalDesc;
+int tdr_naf_tail_infer_local(const TdrNafTailLocalDesc* d, void* stream);
 /* Data-gradient chain of the same half (autograd of :230-238), one launch instead of three:
  *   dt4 = SimpleGate'(W5^T (dout * gamma); t4);  dyn = W4^T dt4;  dy = LayerNorm2d'(dyn; y, mu, rs, lnw) + dout
  * plus the LayerNorm parameter gradients gw = sum dyn * yhat, gb = sum dyn (per-workgroup partials in ws, reduced in a

@@ -1,13 +1,14 @@
 """What the compiler makes of the fused NAFBlock chains and the depthwise stencils, read from the gfx950 assembly -- no GPU needed.
-Units: csrc/tdr_nafblock.hip (training), tdr_nafblock_infer.hip (forward-only), tdr_dyn_infer.hip (modulated forward-only + its stencil)
-and tdr_dwsg.hip, each compiled with the flags csrc/Makefile gives its object.
+Units: csrc/tdr_nafblock.hip (training), tdr_nafblock_infer.hip (forward-only), tdr_dyn_infer.hip (modulated forward-only + its stencil),
+tdr_dwsg.hip and tdr_nafblock_local.hip (the TLSC tail), each compiled with the flags csrc/Makefile gives its object.
   * per unit and kernel: a hash of the instruction stream (labels normalised, comments stripped), instructions, global stores, VGPRs,
     spilled VGPRs, scratch bytes, static LDS bytes, kernarg bytes.  A kernel is keyed by what it is, not by its mangled name:
     chain kernels `tail|head|bwd C=.. KEEP|HEAD=.. sch=.. mod=..`, every other kernel `name<template arguments>`;
   * the training and the forward-only instantiations compiled in ONE translation unit: how many kernels of each set then differ from
     the separately compiled ones (the recorded reason the units are separate).
 Writes profiles/nafchain/isa.json (or `--out PATH`).  `--against OTHER.json` compares the fresh result with a recorded one kernel by
-kernel (hash, VGPRs, spills, scratch, LDS, kernarg bytes) and exits 1 when any differ.
+kernel (hash, VGPRs, spills, scratch, LDS, kernarg bytes) and exits 1 when any differ; a unit the recorded file does not have is
+not compared.
     python profiles/probe_infer_isa.py [--out PATH] [--against PATH] [--hipcc PATH]"""
 import argparse
 import hashlib
@@ -25,8 +26,8 @@ ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'nafchain', 'isa
 ap.add_argument('--against', default=None)
 ap.add_argument('--hipcc', default=os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'))
 a = ap.parse_args()
-UNITS = ['tdr_nafblock', 'tdr_nafblock_infer', 'tdr_dyn_infer', 'tdr_dwsg']
-# the flags of csrc/Makefile for these objects (all four are on its no-SLP list)
+UNITS = ['tdr_nafblock', 'tdr_nafblock_infer', 'tdr_dyn_infer', 'tdr_dwsg', 'tdr_nafblock_local']
+# the flags of csrc/Makefile for these objects (all of them are on its no-SLP list)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-fno-slp-vectorize', '-I' + CSRC,
          '--cuda-device-only', '-S']
 ONE_TU = '#include "tdr_nafblock.hip"\n#include "tdr_nafblock_infer.hip"\n'      # (both include tdr_nafblock_chain.h, once)
@@ -110,7 +111,7 @@ with open(a.out, 'w') as f:
 print(json.dumps(one_tu))
 if a.against:
     other = json.load(open(a.against))['units']
-    diff = {u: differing(units[u], other[u]) + [k for k in other[u] if k not in units[u]] for u in UNITS}
-    print(json.dumps(dict(against=a.against, kernels_compared=sum(len(units[u]) for u in UNITS),
+    diff = {u: differing(units[u], other[u]) + [k for k in other[u] if k not in units[u]] for u in UNITS if u in other}
+    print(json.dumps(dict(against=a.against, kernels_compared=sum(len(units[u]) for u in diff),
                           kernels_that_differ=sum(map(len, diff.values())), differ={u: d for u, d in diff.items() if d})))
     sys.exit(1 if any(diff.values()) else 0)

@@ -15,7 +15,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TDR_LIB_PATH', os.path.join(_HERE, 'libtdr_hip.so'))   # override: profiling probe builds
 
-ABI_VERSION = 111      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
+ABI_VERSION = 112      # csrc/tdr_error.cpp: bumped with every incompatible change of include/tdr.h
 c_fp = C.c_void_p      # device pointers travel as integers
 i32, i64, f32 = C.c_int, C.c_int64, C.c_float
 
@@ -92,6 +92,14 @@ class TdrNafTailDesc(C.Structure):
                 ('b3', c_fp), ('beta', c_fp), ('lnw', c_fp), ('lnb', c_fp), ('b4', c_fp), ('b5', c_fp), ('gamma', c_fp),
                 ('y', c_fp), ('y_ns', i64), ('mu', c_fp), ('rs', c_fp), ('yn', c_fp), ('yn_ns', i64),
                 ('t4', c_fp), ('t4_ns', i64), ('out', c_fp), ('out_ns', i64)]
+
+
+class TdrNafTailLocalDesc(C.Structure):
+    _fields_ = [('N', i32), ('C', i32), ('HW', i32), ('w_fmt', i32), ('eps', f32),
+                ('g', c_fp), ('g_ns', i64), ('pool', c_fp), ('pool_ns', i64), ('x', c_fp), ('x_ns', i64),
+                ('wsca', c_fp), ('w3', c_fp), ('w4', c_fp), ('w5', c_fp),
+                ('bsca', c_fp), ('b3', c_fp), ('beta', c_fp), ('lnw', c_fp), ('lnb', c_fp), ('b4', c_fp), ('b5', c_fp), ('gamma', c_fp),
+                ('out', c_fp), ('out_ns', i64)]
 
 
 class TdrNafTailBwdDesc(C.Structure):
@@ -300,6 +308,7 @@ SIGNATURES = {
     'tdr_naf_head_fwd': (i32, [C.POINTER(TdrNafHeadFwdDesc), c_fp]),
     'tdr_naf_tail_infer': (i32, [C.POINTER(TdrNafTailDesc), c_fp]),
     'tdr_naf_head_infer': (i32, [C.POINTER(TdrNafHeadFwdDesc), c_fp]),
+    'tdr_naf_tail_infer_local': (i32, [C.POINTER(TdrNafTailLocalDesc), c_fp]),
     'tdr_absmax_bits': (i32, [c_fp, i64, i32, i64, c_fp, c_fp]),
     'tdr_pair_sum_partials': (i32, [c_fp, i32, i32, c_fp, c_fp, c_fp, c_fp]),
     'tdr_pair_sum_mid_floats': (i64, [i32, i32]),

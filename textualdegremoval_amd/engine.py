@@ -32,6 +32,9 @@ FUSE_CONV3_DGRAD = True                                                   # conv
 # a forward pass that keeps nothing (keep=False) runs the forward-only chains tdr_naf_head_infer / tdr_naf_tail_infer; False: the training
 # chains, their saved tensors dropped on return (the A/B of profiles/probe_infer.py: what the kernels add to what the walk releases)
 INFER_KERNELS = True
+# a TLSC block (naf_fwd_local) on the fused forward-only chains where the shape allows: tdr_naf_head_infer, then the SCA map and everything
+# after it in tdr_naf_tail_infer_local; False: the per-op launches (the A/B of profiles/probe_tlsc_infer.py)
+LOCAL_KERNELS = True
 
 
 def _sub(P, pre):
@@ -260,11 +263,25 @@ def naf_fwd_local(x, P, k1, k2):
     becomes a per-pixel map, so `x * sca(x)` (:192) is an element-wise product of two maps, folded into conv3's operand load as
     the gate product of the concatenation [g ; sca(pool(g))].  Inference only (the reference wraps the network in eval /
     no_grad, network_nafnet_guided_arch.py:756-768).  Where the box covers the whole map the reference falls back to
-    F.adaptive_avg_pool2d(x, 1) (:43-44): that is the ordinary block."""
+    F.adaptive_avg_pool2d(x, 1) (:43-44): that is the ordinary block, run as a pass that keeps nothing.
+    Where the fused chains take the shape (LOCAL_KERNELS) the block is four launches' worth of calls -- head chain, depthwise + gate,
+    box mean, and tdr_naf_tail_infer_local, which forms the attention map from the box mean itself and walks conv3 .. conv5: no
+    concatenation buffer, no copy, no separate sca / LayerNorm launches."""
     N, c, H, W = x.shape
     if k1 >= H and k2 >= W:
-        return naf_fwd(x, P)[0]
+        return naf_fwd(x, P, keep=False)[0]
     wp, mp, *_ = K.pack_weights(P['conv1.weight'], PACK_FWD)
+    if LOCAL_KERNELS and K.naf_tail_supported(c, H * W) and wp.fmt in (K.FMT_HX2, K.FMT_BX3) and x.is_contiguous():
+        if FUSE_HEAD:
+            t1 = K.naf_head_infer(x, P['norm1.weight'], P['norm1.bias'], LN_EPS, wp, P['conv1.bias'])
+        else:
+            t1 = K.conv_forward(K.layernorm2d_fwd(x, P['norm1.weight'], P['norm1.bias'], LN_EPS)[0], wp, mp, 2 * c, 1, bias=P['conv1.bias'])
+        g = K.dwsg_fwd(t1, P['conv2.weight'], P['conv2.bias'])[0]
+        t1 = None                                          # (each intermediate goes once its last consumer is enqueued, as in naf_fwd)
+        pooled = K.local_avgpool(g, k1, k2)
+        wsp, w3p, w4p, w5p = (K.pack_weights(P[k], PACK_FWD)[0] for k in ('sca.1.weight', 'conv3.weight', 'conv4.weight', 'conv5.weight'))
+        return K.naf_tail_infer_local(g, pooled, x, wsp, P['sca.1.bias'], w3p, P['conv3.bias'], P['beta'].view(-1), P['norm2.weight'],
+                                      P['norm2.bias'], LN_EPS, w4p, P['conv4.bias'], w5p, P['conv5.bias'], P['gamma'].view(-1))
     xn, _, _ = K.layernorm2d_fwd(x, P['norm1.weight'], P['norm1.bias'], LN_EPS)
     t1 = K.conv_forward(xn, wp, mp, 2 * c, 1, bias=P['conv1.bias'])
     g, _ = K.dwsg_fwd(t1, P['conv2.weight'], P['conv2.bias'])

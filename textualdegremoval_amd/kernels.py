@@ -993,6 +993,24 @@ def naf_tail_infer(g, s, x, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamm
     return out
 
 
+def naf_tail_infer_local(g, pooled, x, wscap, bsca, w3p, b3, beta, lnw, lnb, eps, w4p, b4, w5p, b5, gamma):
+    """naf_tail_infer for a TLSC block (csrc/tdr_nafblock_local.hip): the channel attention is the per-pixel map wsca pooled + bsca,
+    formed in the kernel (pooled [N, c, H, W]: local_avgpool(g)) -> out alone"""
+    N, Cc, H, W = g.shape
+    assert pooled.shape == g.shape and x.shape == g.shape and g.is_contiguous() and pooled.is_contiguous() and x.is_contiguous()
+    assert wscap.fmt == w3p.fmt == w4p.fmt == w5p.fmt
+    out = torch.empty_like(g)
+    d = _lib.TdrNafTailLocalDesc()
+    d.N, d.C, d.HW, d.w_fmt, d.eps = N, Cc, H * W, w3p.fmt, float(eps)
+    d.g, d.g_ns, d.pool, d.pool_ns, d.x, d.x_ns = g.data_ptr(), _dense_nchw(g), pooled.data_ptr(), _dense_nchw(pooled), x.data_ptr(), _dense_nchw(x)
+    d.wsca, d.w3, d.w4, d.w5 = wscap.data_ptr(), w3p.data_ptr(), w4p.data_ptr(), w5p.data_ptr()
+    d.bsca, d.b3, d.beta, d.lnw, d.lnb = bsca.data_ptr(), b3.data_ptr(), beta.data_ptr(), lnw.data_ptr(), lnb.data_ptr()
+    d.b4, d.b5, d.gamma = b4.data_ptr(), b5.data_ptr(), gamma.data_ptr()
+    d.out, d.out_ns = out.data_ptr(), _dense_nchw(out)
+    check(_lib.load().tdr_naf_tail_infer_local(C.byref(d), _stream()), 'tdr_naf_tail_infer_local')
+    return out
+
+
 def _ln_partials_finish(ws, nparts, Cc):
     """Finisher that reduces the per-workgroup LayerNorm-gradient partials a fused NAFBlock backward left in its PRIVATE `ws`"""
     def fin():

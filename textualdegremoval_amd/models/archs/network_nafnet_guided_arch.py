@@ -278,11 +278,16 @@ class NAFNetLocal(NAFNet):
         self.eval()
 
     def forward(self, inp):
+        from ... import kernels as K
         require_gpu(inp, 'NAFNetLocal')
         names, params = _named(self)
-        with torch.no_grad():
-            out, _ = E.unet_fwd(dict(zip(names, [p.detach() for p in params])), self.cfg, inp.detach(), local=self.ksizes)
-        return out
+        # a pass that keeps nothing, its weights packed outside any PackPlan (as nafnet_arch_utils.infer_fwd runs one)
+        prev = K.set_pack_plan(None)
+        try:
+            with torch.no_grad():
+                return E.unet_fwd(dict(zip(names, [p.detach() for p in params])), self.cfg, inp.detach(), local=self.ksizes, keep=False)[0]
+        finally:
+            K.set_pack_plan(prev)
 
 
 class NAFNetLocal_RefFusion(NAFNetRefFusion):
