@@ -22,7 +22,9 @@ extern "C" {
 
 /* C-ABI version: bumped with every incompatible change of this header (100 rounds 1-2, 101 round 3, 102 round 4, 103 - 104
  * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
- * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local); the
+ * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local; still 112,
+ * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes -- no existing entry point or descriptor changed, and the binding resolves
+ * every declared symbol when it loads the library, so a build without them is refused there); the
  * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
 #define TDR_ABI_VERSION 112
 int tdr_version(void);
@@ -117,6 +119,14 @@ int tdr_pack_weights_hx2(const float* w, int Cout, int Cin, int KH, int mode, vo
 /* tuning aid (profiles/autotune_conv.py): force tile configuration `cfg` (0 = built-in heuristic) of the split-bf16
  * forward kernels with kernel size kh == 1, or of the 3x3 / 2x2 ones (any other kh) */
 int tdr_conv_force_cfg(int kh, int cfg);
+/* The float4-staged 1x1 kernel of the split-bf16 arithmetic (csrc/tdr_conv_bx3.hip, conv1x1_bx3s_kernel): 1x1 / stride-1 launches
+ * with whole aligned pixel quads (W % 4 == 0, 16-byte aligned `in`, in_ns % 4 == 0), pad 0, at least four K stages of the tile's stage
+ * length run on it instead of the generic kernel, with bit-identical results; a forced tile configuration
+ * (tdr_conv_force_cfg(1, cfg != 0)) and EPI_PSHUF stay on the generic kernel.  `_set(0)` turns it off (cross-check tests, A/B runs),
+ * `_set(1)` on again (the default).  `_takes` walks the dispatch of tdr_conv_forward for `d` without launching anything: 1 if the
+ * staged kernel would run it under the current switch and forced configuration, else 0 (any other format or kernel size included). */
+int tdr_conv1x1_bx3_staged_set(int on);
+int tdr_conv1x1_bx3_staged_takes(const TdrConvDesc* d);
 /* Multi-tensor packing: one launch packs every (weight, mode, format) job of a step.
  * The caller fills jobs with tdr_pack_job_init (host), sets first_block = running sum of ceil(total/256),
  * copies the array to the device and launches with total_blocks = the final sum. */

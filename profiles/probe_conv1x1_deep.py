@@ -1,6 +1,7 @@
 """1x1 convolutions of the C = 512 / 1024 levels (3 NAFBlocks at 32 x 32, N = 4: 4096 pixels, up to 2048 x 1024 weights) on conv_bx3_kernel under
 the default arithmetic, per forced tile configuration (tdr_conv_force_cfg(1, cfg): 0 heuristic, 1 128x128, 2 64x256, 3 64x128, 4 32x256, 5 256x64;
-co x pixels).  A launch streams the whole weight pack once per pixel tile: (pixels / tile) x |W| bytes from L2 / MALL.
+co x pixels; c0 is the float4-staged kernel conv1x1_bx3s_kernel where the dispatch takes the shape -- marked `s` -- and g0 the same heuristic
+configuration with kernels.CONV1X1_STAGED off, i.e. the generic kernel: the pair to compare).  A launch streams the whole weight pack once per pixel tile: (pixels / tile) x |W| bytes from L2 / MALL.
 usage: python profiles/probe_conv1x1_deep.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,8 +21,10 @@ def t(N, Cin, Cout, H, mode):
     outs = [torch.empty(N, co, H, H, device='cuda') for _ in range(2)]
     line = f'1x1 {Cin}->{Cout} @{H} N{N} {"fwd  " if mode == K.PACK_FWD else "dgrad"}:'
     flop = 2.0 * N * Cin * Cout * H * H
-    for cfg in (0, 1, 2, 3, 4, 5):
-        lib.tdr_conv_force_cfg(1, cfg)
+    for cfg in (-1, 0, 1, 2, 3, 4, 5):
+        K.CONV1X1_STAGED = cfg != -1                                   # -1: heuristic configuration on the generic kernel (g0)
+        lib.tdr_conv_force_cfg(1, max(cfg, 0))
+        staged = K.conv1x1_staged_takes(xin[0], wp, mp, co, 1, pad=0, out=outs[0])
         f = lambda i: K.conv_forward(xin[i & 1], wp, mp, co, 1, pad=0, out=outs[i & 1])
         for i in range(3): f(i)
         torch.cuda.synchronize()
@@ -36,7 +39,7 @@ def t(N, Cin, Cout, H, mode):
         for _ in range(5): g.replay()
         e1.record(); torch.cuda.synchronize()
         us = e0.elapsed_time(e1) / 100 * 1e3
-        line += f'  c{cfg} {us:6.1f} us ({flop / us * 1e-6:4.0f} TF)'
+        line += f'  {"g0" if cfg < 0 else f"c{cfg}"}{"s" if staged else " "} {us:6.1f} us ({flop / us * 1e-6:4.0f} TF)'
     lib.tdr_conv_force_cfg(1, 0)
     print(line, flush=True)
 

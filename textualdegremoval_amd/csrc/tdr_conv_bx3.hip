@@ -552,6 +552,197 @@ int launch_c1_hx2(const ConvArgs& a, int N, hipStream_t st) {
     return TDR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// 1x1 / stride 1 / 3-way bf16 split (the default arithmetic) with 16-byte operand loads.
+//
+// The float4-staged form of conv_bx3_kernel<1, 1, ..., SCH_BX3>: same weight fragments, same [plane][octet][pixel] LDS slots
+// (XOR-swizzled as above), same six products per 16-channel group in the same order into the same accumulators, same
+// epilogues -- the output is bit-identical to the generic kernel at the same tile configuration.  Only the staging differs.
+// Three planes of a stage must fit twice into 64 KiB (two workgroups per CU, double buffered), so a stage is 24 KiB:
+// 512 slots = KS x NPX / 8, i.e. KS = 4096 / NPX channels (32 for a 128-pixel tile, 64 for 64 pixels, 16 for 256).  That is
+// half a (octet, quad) task per thread, and every thread takes half an octet: 4 channels x 4 adjacent pixels = four float4
+// loads, split in registers exactly as store_group does (same pin: every plane from one fp32 value), written as the 8-byte
+// halves of the 16-byte slots (twelve ds_write_b64 per stage; per 32 channels the generic pipeline issues 16 dword loads,
+// six ds_write_b128 and two barriers per thread, this one 4 loads, 12 half-slot writes and one barrier).  Operand loads run
+// two stages ahead in two register sets.
+// ---------------------------------------------------------------------------------------------------------------
+template <int WM, int TM, int TN, int EPI, bool GATE>
+__global__ __launch_bounds__(256, 2) void conv1x1_bx3s_kernel(ConvArgs a) {
+    constexpr int NS = 3, NP = 6;
+    constexpr int WN = 4 / WM;
+    constexpr int BM = 32 * TM * WM;
+    constexpr int NT = TN * WN;
+    constexpr int NPX = 32 * NT;          // pixels per tile
+    constexpr int QUADS = NPX / 4;        // float4 pixel quads per tile
+    constexpr int HOCT = 256 / QUADS;     // 4-channel half octets staged per pass: one (half octet, quad) task per thread
+    constexpr int KS = 4 * HOCT;          // channels per stage
+    constexpr int OCT = KS / 8;           // octets per stage
+    constexpr int GPS = KS / 16;          // 16-channel MFMA groups per stage
+    constexpr int PFD = 2;                // stages of operand loads in flight (register sets)
+    static_assert(GPS >= 1 && NS * OCT * NPX * 16 == 24576, "a stage is 24 KiB");
+
+    extern __shared__ __attribute__((aligned(16))) uint4 smem4[];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const int j = lane & 31, kk = lane >> 5;
+    const int TW = 1 << a.tw_log2, SR = 32 >> a.tw_log2, TH = NT * SR;
+    int logical;
+    {   // XCD-aware block order, as in conv_bx3_kernel
+        const int T = gridDim.x, b = blockIdx.x;
+        const int q = T >> 3, r = T & 7, xcd = b & 7, slot = b >> 3;
+        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    }
+    const int mtile = logical % a.mtiles, ptile = logical / a.mtiles;
+    const int tx = ptile % a.tiles_x, ty = ptile / a.tiles_x;
+    const int m0 = mtile * BM;
+    const int n = blockIdx.z;
+    const int oy0 = ty * TH, ox0 = tx * TW;
+    const long HWin = (long)a.H * a.W;
+
+    // ---- staging task of this thread: half octet sh (channels 4 sh .. 4 sh + 3 of the stage), pixel quad sq
+    const int sh = tid / QUADS, sq = tid % QUADS;
+    const int p0 = 4 * sq;
+    const int gy = oy0 + (p0 >> a.tw_log2), gx = ox0 + (p0 & (TW - 1));
+    const bool pok = gy < a.H && gx < a.W;            // W % 4 == 0: a quad is inside or outside as a whole
+    const long goff = pok ? (long)gy * a.W + gx : 0;
+    const float* in_n = a.in + (long)n * a.in_ns;
+    const float* ks_n = a.kscale ? a.kscale + (long)n * a.kscale_ns : nullptr;
+    const int ngroups = (a.Cin + 15) >> 4;
+    const int nstages = (a.Cin + KS - 1) / KS;
+
+    float4 rin[PFD][4];
+    float4 rin2[GATE ? PFD : 1][GATE ? 4 : 1];
+    float rks[PFD][4];
+    auto load_stage = [&](int st, int set) {
+        const int cbase = st * KS + sh * 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int ci = cbase + i;
+            rin[set][i] = make_float4(0.f, 0.f, 0.f, 0.f);      // outside the image / past Cin: exact zeros in every plane
+            rks[set][i] = 1.f;
+            if (GATE) rin2[set][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (pok && ci < a.Cin) {
+                const float* src = in_n + (long)ci * HWin + goff;
+                rin[set][i] = *reinterpret_cast<const float4*>(src);
+                if (GATE) rin2[set][i] = *reinterpret_cast<const float4*>(src + a.gate_off);
+                if (ks_n) rks[set][i] = ks_n[ci];
+            }
+        }
+    };
+    int wslot[4];                                     // in 8-byte units: 16-byte slot, half sh & 1
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wslot[i] = 2 * ((sh >> 1) * NPX + swz1(p0 + i)) + (sh & 1);
+    auto store_stage = [&](int set, int buf) {
+        uint2* sb = reinterpret_cast<uint2*>(smem4 + buf * (NS * OCT * NPX));
+#pragma unroll
+        for (int px = 0; px < 4; ++px) {
+            union { uint2 u; __bf16 v[4]; } h, m, l;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float4 q4 = rin[set][i];
+                float v = px == 0 ? q4.x : (px == 1 ? q4.y : (px == 2 ? q4.z : q4.w));
+                if (GATE) {
+                    const float4 g4 = rin2[set][i];
+                    v *= px == 0 ? g4.x : (px == 1 ? g4.y : (px == 2 ? g4.z : g4.w));
+                }
+                v *= rks[set][i];
+                asm volatile("" : "+v"(v));            // pin: every split plane from the same fp32 value (conv_bx3_kernel)
+                __bf16 hh, mm, ll;
+                split3(v, hh, mm, ll);
+                h.v[i] = hh; m.v[i] = mm; l.v[i] = ll;
+            }
+            sb[wslot[px]] = h.u;
+            sb[2 * (OCT * NPX) + wslot[px]] = m.u;
+            sb[4 * (OCT * NPX) + wslot[px]] = l.u;
+        }
+    };
+
+    // ---- fragment addresses
+    int bslot[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) bslot[tn] = kk * NPX + swz1(32 * (wn * TN + tn) + j);
+    const int MT = a.Mpad >> 5;
+    const uint4* wfrag[TM];
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+        const int mt = min((m0 >> 5) + wm * TM + tm, MT - 1);
+        wfrag[tm] = reinterpret_cast<const uint4*>(a.wp) + (long)n * (a.wp_ns >> 2) + (long)mt * (NS * 64) + lane;
+    }
+    const long wstep = (long)MT * (NS * 64);
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+
+    Frag af[TM][NS], afn[TM][NS];
+    auto load_a = [&](Frag (&dst)[TM][NS], long g) {
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) dst[tm][s].u = wfrag[tm][g * wstep + s * 64];
+    };
+
+    load_a(af, 0);
+#pragma unroll
+    for (int p = 0; p < PFD; ++p)
+        if (p < nstages) load_stage(p, p);
+    store_stage(0, 0);
+    __syncthreads();
+
+    for (int s0 = 0; s0 < nstages; s0 += PFD) {
+#pragma unroll
+        for (int u = 0; u < PFD; ++u) {
+            const int st = s0 + u;
+            if (st < nstages) {
+                const int buf = st & 1;
+                const uint4* sb = smem4 + buf * (NS * OCT * NPX);
+#pragma unroll
+                for (int gg = 0; gg < GPS; ++gg) {
+                    const int g = st * GPS + gg;
+                    if (g < ngroups) {
+                        load_a(afn, min(g + 1, ngroups - 1));
+                        // set u is free (stage st already sits in LDS): the loads of stage st + PFD go out behind the
+                        // first weight-fragment prefetch, so the in-order wait for the fragments leaves them in flight
+                        if (gg == 0 && st + PFD < nstages) load_stage(st + PFD, u);
+                        Frag bf[TN][NS];
+#pragma unroll
+                        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) bf[tn][s].u = sb[s * (OCT * NPX) + 2 * gg * NPX + bslot[tn]];
+                        constexpr int SA[6] = {2, 0, 1, 1, 0, 0}, SB[6] = {0, 2, 1, 0, 1, 0};   // lh hl mm mh hm hh (conv_bx3_kernel)
+#pragma unroll
+                        for (int q = 0; q < NP; ++q)
+#pragma unroll
+                            for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                                for (int tn = 0; tn < TN; ++tn)
+                                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[tm][SA[q]].v, bf[tn][SB[q]].v, acc[tm][tn], 0, 0, 0);
+#pragma unroll
+                        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) af[tm][s] = afn[tm][s];
+                    }
+                }
+                if (st + 1 < nstages) store_stage((u + 1) % PFD, buf ^ 1);
+                __syncthreads();
+            }
+        }
+    }
+
+    if constexpr (EPI != EPI_PSHUF) {
+        if (a.vec_epi) {
+            conv_epilogue_vec<TM, TN, EPI>(a, acc, n, m0, wm, wn, oy0, ox0, lane, reinterpret_cast<float*>(smem4) + wave * (32 * 36));
+            return;
+        }
+    }
+    conv_epilogue<TM, TN, EPI>(a, acc, n, m0, wm, wn, oy0, ox0, j, kk);
+}
+
 // 16-byte staging needs whole, aligned pixel quads; it pays from four stages of K on and for launches of a single
 // round of workgroups (probe_conv1x1.py / kernel traces on MI355X: 256->512 @64x64 N=4 30.1 -> 27.0 us, 512->256 37.9
 // -> 32.2 us; 128->256 @256x256 with two stages 123 -> 134 us, 64->128 @512x512 with one stage 189 -> 226 us; 2048
@@ -567,8 +758,50 @@ inline bool c1_hx2_ok(const ConvArgs& a, int npx, int bm, int N) {
            a.H == a.OH && a.W == a.OW;
 }
 
+template <int WM, int TM, int TN, int EPI, bool GATE>
+int launch_c1_bx3s(const ConvArgs& a, int N, hipStream_t st) {
+    constexpr int WN = 4 / WM;
+    constexpr int BM = 32 * TM * WM;
+    constexpr int NT = TN * WN;
+    const int TW = 1 << a.tw_log2, SR = 32 >> a.tw_log2, TH = NT * SR;
+    ConvArgs b = a;
+    b.tiles_x = tdr_cdiv(a.OW, TW);
+    const int tiles_y = tdr_cdiv(a.OH, TH);
+    b.mtiles = tdr_cdiv(a.Cout, BM);
+    dim3 grid(b.tiles_x * tiles_y * b.mtiles, 1, N);
+    b.single_buf = 0;
+    const size_t lds = 2 * 24576;        // two stages of 3 planes x 512 slots x 16 B (above the vector epilogue's 18 KiB)
+    hipLaunchKernelGGL((conv1x1_bx3s_kernel<WM, TM, TN, EPI, GATE>), grid, dim3(256), lds, st, b);
+    TDR_LAUNCH_CHECK("conv1x1_bx3s_kernel");
+    return TDR_OK;
+}
+
+// tile-configuration override for profiles/autotune_conv.py: [0] 1x1 kernels, [1] 3x3 / 2x2 kernels; 0 = heuristic
+int g_force_cfg[2] = {tdr_tune_env("TDR_BX_CFG1") ? atoi(tdr_tune_env("TDR_BX_CFG1")) : 0, tdr_tune_env("TDR_BX_CFG3") ? atoi(tdr_tune_env("TDR_BX_CFG3")) : 0};
+int g_c1_bx3_staged = 1;          // tdr_conv1x1_bx3_staged_set: 0 keeps every bx3 1x1 launch on conv_bx3_kernel
+thread_local int* g_c1_bx3_query = nullptr;    // tdr_conv1x1_bx3_staged_takes: the dispatch below, on the asking thread only, records its decision here and launches nothing
+
+// The eligibility rule of c1_hx2_ok with the stage length of the 24 KiB bx3 stage (4096 / npx channels), for the heuristic's own
+// tile configuration only: a forced one (tdr_conv_force_cfg(1, cfg != 0)) names a configuration of conv_bx3_kernel and stays there.
+// No workgroup cap (the hx2 form has one at 512): launches of 1024 - 8192 workgroups measured 7 - 21 % faster than the generic kernel as
+// well, at the same two workgroups per CU (profiles/conv1x1_bx3/README.md; tuning builds: TDR_C1_BLOCKS sets a cap).
+// The 256-pixel tiles (16-channel stages: the generic kernel's barrier count, only the wider loads) measured 3 - 12 % faster and stay in.
+inline bool c1_bx3_ok(const ConvArgs& a, int npx, int bm, int N) {
+    static const long max_blocks = tdr_tune_env("TDR_C1_BLOCKS") ? atol(tdr_tune_env("TDR_C1_BLOCKS")) : (1L << 40);
+    const int ks = 4096 / npx;
+    const long blocks = (long)tdr_cdiv((long)a.OH * a.OW, npx) * tdr_cdiv(a.Cout, bm) * N;
+    return g_c1_bx3_staged && g_force_cfg[0] == 0 && blocks <= max_blocks && (a.Cin + ks - 1) / ks >= 4 && a.pad == 0 && a.W % 4 == 0 && a.in_ns % 4 == 0 &&
+           (reinterpret_cast<uintptr_t>(a.in) & 15) == 0 && a.H == a.OH && a.W == a.OW;
+}
+
 template <int KH, int S, int WM, int TM, int TN, int EPI, bool GATE, int SCH>
 int launch_bx_cfg_s(const ConvArgs& a, int N, hipStream_t st) {
+    if constexpr (KH == 1 && S == 1 && SCH == SCH_BX3 && EPI != EPI_PSHUF) {
+        const bool staged = c1_bx3_ok(a, 32 * TN * (4 / WM), 32 * TM * WM, N);
+        if (g_c1_bx3_query) { *g_c1_bx3_query = staged ? 1 : 0; return TDR_OK; }
+        if (staged) return launch_c1_bx3s<WM, TM, TN, EPI, GATE>(a, N, st);
+    }
+    if (g_c1_bx3_query) return TDR_OK;    // any other launch: the query's answer stays 0
     if constexpr (KH == 1 && S == 1 && SCH != SCH_BX3 && EPI != EPI_PSHUF)
         if (c1_hx2_ok(a, 32 * TN * (4 / WM), 32 * TM * WM, N)) return launch_c1_hx2<WM, TM, TN, EPI, GATE, SCH>(a, N, st);
     constexpr int NS = SCH == SCH_BX3 ? 3 : (SCH == SCH_HX2 ? 2 : 1);
@@ -631,9 +864,6 @@ int launch_bx_cfg_s(const ConvArgs& a, int N, hipStream_t st) {
     TDR_LAUNCH_CHECK("conv_bx3_kernel");
     return TDR_OK;
 }
-
-// tile-configuration override for profiles/autotune_conv.py: [0] 1x1 kernels, [1] 3x3 / 2x2 kernels; 0 = heuristic
-int g_force_cfg[2] = {tdr_tune_env("TDR_BX_CFG1") ? atoi(tdr_tune_env("TDR_BX_CFG1")) : 0, tdr_tune_env("TDR_BX_CFG3") ? atoi(tdr_tune_env("TDR_BX_CFG3")) : 0};
 
 template <int KH, int S, int WM, int TM, int TN, int EPI, bool GATE>
 int launch_bx_cfg(const ConvArgs& a, int N, hipStream_t st) {
@@ -712,6 +942,22 @@ __global__ void pack_weights_hx2_kernel(const float* __restrict__ w, int Cout, i
 extern "C" int tdr_conv_force_cfg(int kh, int cfg) {
     g_force_cfg[kh == 1 ? 0 : 1] = cfg;
     return TDR_OK;
+}
+
+extern "C" int tdr_conv1x1_bx3_staged_set(int on) {
+    g_c1_bx3_staged = on ? 1 : 0;
+    return TDR_OK;
+}
+
+// tdr_conv_forward itself (its argument checks included), walked without a launch: the query pointer is per thread, so a convolution
+// issued from another thread meanwhile is launched as usual
+extern "C" int tdr_conv1x1_bx3_staged_takes(const TdrConvDesc* d) {
+    if (!d || d->wp_fmt != 1 || d->dil != 1 || d->KH != 1 || d->stride != 1) return 0;
+    int takes = 0;
+    g_c1_bx3_query = &takes;
+    const int rc = tdr_conv_forward(d, nullptr);
+    g_c1_bx3_query = nullptr;
+    return rc == TDR_OK ? takes : 0;
 }
 
 extern "C" int64_t tdr_packed_weight_bytes_bx3(int M, int Kch, int KH_eff) {

@@ -131,6 +131,9 @@ ATTN_F32 = False              # exact-fp32 attention products inside an fp16 ari
 ATTN_BX3 = True               # TDR_MATH=bx3: the frozen ViTs' attention on the 3-way bf16 split (False: exact fp32 MFMA, as in rounds 1 - 5)
 DWK_GENERIC = False           # the LDS-tiled generic depthwise kernels instead of the register-window ones (module switch: cross-check tests)
 SIDE_WGRAD = False            # (module switch: tests/test_hip_network.py::test_side_stream_weight_gradients_match)
+CONV1X1_STAGED = True         # TDR_MATH=bx3: eligible 1x1 launches on the float4-staged kernel (False: all on the generic kernel; conv_forward passes the
+                              # switch on to the library -- tdr_conv1x1_bx3_staged_set -- whenever it changed; bit-identical either way)
+_conv1x1_staged_sent = True   # the library's own default
 _side_stream = None
 _side_active = False
 _side_dirty = False
@@ -467,10 +470,10 @@ def pack_patches(blk, G, PH, PW, pstep, dil, off):
     return wp, (M + 31) // 32 * 32, per_b
 
 
-def conv_forward(x, wp, Mpad, Cout, KH, stride=1, dil=1, pad=0, OH=None, OW=None, out=None, Cin=None, epi=EPI_STD,
-                 gate=False, kscale=None, wp_ns=0, bias=None, scale=None, bias2=None, bias2_mul=1.0, res=None,
-                 mask=None, aux=None, relu=False):
-    lib = _lib.load()
+def _conv_desc(x, wp, Mpad, Cout, KH, stride=1, dil=1, pad=0, OH=None, OW=None, out=None, Cin=None, epi=EPI_STD,
+               gate=False, kscale=None, wp_ns=0, bias=None, scale=None, bias2=None, bias2_mul=1.0, res=None,
+               mask=None, aux=None, relu=False):
+    """-> (TdrConvDesc of the launch, its output tensor): the arguments of conv_forward"""
     N, Cx, H, W = x.shape
     if Cin is None:
         Cin = Cx // 2 if gate else Cx
@@ -502,10 +505,36 @@ def conv_forward(x, wp, Mpad, Cout, KH, stride=1, dil=1, pad=0, OH=None, OW=None
     d.mask, d.mask_ns = _p(mask), (_dense_nchw(mask) if mask is not None else 0)
     d.aux, d.aux_ns = _p(aux), (_dense_nchw(aux) if aux is not None else 0)
     d.relu = int(relu) if not isinstance(relu, bool) else (1 if relu else 0)      # 2 = exact GELU
+    return d, out
+
+
+def _sync_conv1x1_staged(lib):
+    global _conv1x1_staged_sent
+    if bool(CONV1X1_STAGED) != _conv1x1_staged_sent:
+        check(lib.tdr_conv1x1_bx3_staged_set(1 if CONV1X1_STAGED else 0), 'tdr_conv1x1_bx3_staged_set')
+        _conv1x1_staged_sent = bool(CONV1X1_STAGED)
+
+
+def conv_forward(x, wp, Mpad, Cout, KH, stride=1, dil=1, pad=0, OH=None, OW=None, out=None, Cin=None, epi=EPI_STD,
+                 gate=False, kscale=None, wp_ns=0, bias=None, scale=None, bias2=None, bias2_mul=1.0, res=None,
+                 mask=None, aux=None, relu=False):
+    lib = _lib.load()
+    d, out = _conv_desc(x, wp, Mpad, Cout, KH, stride, dil, pad, OH, OW, out, Cin, epi, gate, kscale, wp_ns, bias, scale, bias2,
+                        bias2_mul, res, mask, aux, relu)
     if _survey is not None and d.wp_fmt in (FMT_HX2, FMT_H1):
         _survey.probe(x, 'grad' if BACKWARD_PHASE else 'fwd')
+    _sync_conv1x1_staged(lib)
     check(lib.tdr_conv_forward(C.byref(d), _stream()), 'tdr_conv_forward')
     return out
+
+
+def conv1x1_staged_takes(x, wp, Mpad, Cout, KH, *args, **kw):
+    """(arguments: exactly those of conv_forward)  True if conv_forward with the same arguments would run on the float4-staged 1x1 kernel of the bx3 arithmetic (under the current
+    CONV1X1_STAGED and forced tile configuration); launches nothing.  Pass `out=` to ask about a particular output view."""
+    lib = _lib.load()
+    d, _ = _conv_desc(x, wp, Mpad, Cout, KH, *args, **kw)
+    _sync_conv1x1_staged(lib)
+    return bool(lib.tdr_conv1x1_bx3_staged_takes(C.byref(d)))
 
 
 class P16:
