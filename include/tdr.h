@@ -119,12 +119,13 @@ int tdr_pack_weights_hx2(const float* w, int Cout, int Cin, int KH, int mode, vo
 /* tuning aid (profiles/autotune_conv.py): force tile configuration `cfg` (0 = built-in heuristic) of the split-bf16
  * forward kernels with kernel size kh == 1, or of the 3x3 / 2x2 ones (any other kh) */
 int tdr_conv_force_cfg(int kh, int cfg);
-/* The float4-staged 1x1 kernel of the split-bf16 arithmetic (csrc/tdr_conv_bx3.hip, conv1x1_bx3s_kernel): 1x1 / stride-1 launches
- * with whole aligned pixel quads (W % 4 == 0, 16-byte aligned `in`, in_ns % 4 == 0), pad 0, at least four K stages of the tile's stage
- * length run on it instead of the generic kernel, with bit-identical results; a forced tile configuration
- * (tdr_conv_force_cfg(1, cfg != 0)) and EPI_PSHUF stay on the generic kernel.  `_set(0)` turns it off (cross-check tests, A/B runs),
+/* The float4-staged 1x1 kernel, any arithmetic (csrc/tdr_conv_bx3.hip, conv1x1_staged_kernel; wp_fmt 1, 2 and 3 -- the names keep the
+ * `bx3` of the format they were added for): 1x1 / stride-1 launches with whole aligned pixel quads (W % 4 == 0, 16-byte aligned `in`,
+ * in_ns % 4 == 0), pad 0, at least four K stages of the tile's stage length run on it instead of the generic kernel, with bit-identical
+ * results; wp_fmt 1: a forced tile configuration (tdr_conv_force_cfg(1, cfg != 0)) stays on the generic kernel; wp_fmt 2 / 3: launches of
+ * more than 512 workgroups do; EPI_PSHUF does for every format.  `_set(0)` turns it off for every format (cross-check tests, A/B runs),
  * `_set(1)` on again (the default).  `_takes` walks the dispatch of tdr_conv_forward for `d` without launching anything: 1 if the
- * staged kernel would run it under the current switch and forced configuration, else 0 (any other format or kernel size included). */
+ * staged kernel would run it under the current switch and forced configuration, else 0 (wp_fmt 0 or any other kernel size included). */
 int tdr_conv1x1_bx3_staged_set(int on);
 int tdr_conv1x1_bx3_staged_takes(const TdrConvDesc* d);
 /* Multi-tensor packing: one launch packs every (weight, mode, format) job of a step.

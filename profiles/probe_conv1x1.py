@@ -1,4 +1,4 @@
-"""Ablation timing of conv1x1_hx2_kernel (profiling builds libtdr_probeNN.so, see csrc/tdr_conv_bx3.hip TDR_PROBE 11-15).
+"""Ablation timing of the float4-staged 1x1 kernel under hx2, conv1x1_staged_kernel<..., SCH_HX2> (profiling builds libtdr_probeNN.so, see csrc/tdr_conv_bx3.hip TDR_PROBE 11-15).
 usage: TDR_LIB_PATH=textualdegremoval_amd/libtdr_probeNN.so python profiles/probe_conv1x1.py
 Each shape is timed inside a hipGraph of 40 back-to-back launches on two alternating input buffers (cold-ish L2)."""
 import os, sys

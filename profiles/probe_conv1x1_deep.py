@@ -1,6 +1,6 @@
 """1x1 convolutions of the C = 512 / 1024 levels (3 NAFBlocks at 32 x 32, N = 4: 4096 pixels, up to 2048 x 1024 weights) on conv_bx3_kernel under
 the default arithmetic, per forced tile configuration (tdr_conv_force_cfg(1, cfg): 0 heuristic, 1 128x128, 2 64x256, 3 64x128, 4 32x256, 5 256x64;
-co x pixels; c0 is the float4-staged kernel conv1x1_bx3s_kernel where the dispatch takes the shape -- marked `s` -- and g0 the same heuristic
+co x pixels; c0 is the float4-staged kernel conv1x1_staged_kernel<..., SCH_BX3> where the dispatch takes the shape -- marked `s` -- and g0 the same heuristic
 configuration with kernels.CONV1X1_STAGED off, i.e. the generic kernel: the pair to compare).  A launch streams the whole weight pack once per pixel tile: (pixels / tile) x |W| bytes from L2 / MALL.
 usage: python profiles/probe_conv1x1_deep.py"""
 import os, sys

@@ -1,5 +1,5 @@
 """Launches of more than one round of workgroups, and the 256-pixel tiles (16-channel stages), on the float4-staged bx3 1x1 kernel against the
-generic kernel (kernels.CONV1X1_STAGED on / off; c1_bx3_ok in csrc/tdr_conv_bx3.hip has no workgroup cap -- these lines are why).  A cap can
+generic kernel (kernels.CONV1X1_STAGED on / off; c1_staged_ok<SCH_BX3> in csrc/tdr_conv_bx3.hip has no workgroup cap -- these lines are why).  A cap can
 be tried in a TUNING build of the library:
     make -C textualdegremoval_amd/csrc variant VFILE=tdr_conv_bx3 VFLAGS=-DTDR_TUNING_KNOBS VOUT=../libtdr_hip_tune.so
     TDR_LIB_PATH=textualdegremoval_amd/libtdr_hip_tune.so TDR_C1_BLOCKS=512 python profiles/probe_conv1x1_staged_cap.py

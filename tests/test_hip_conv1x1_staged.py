@@ -1,18 +1,23 @@
-"""The float4-staged 1x1 kernel of the default (bx3) arithmetic, conv1x1_bx3s_kernel (csrc/tdr_conv_bx3.hip), against the generic
+"""The float4-staged 1x1 kernel, conv1x1_staged_kernel (csrc/tdr_conv_bx3.hip), of every arithmetic (bx3, hx2, h1) against the generic
 conv_bx3_kernel it replaces on eligible launches.  The two differ in how the pixels reach the LDS planes and in nothing else -- same
-weight fragments, same six products per 16-channel group in the same order, same accumulators and epilogues -- so every case asserts
-BIT equality (torch.equal) between the launch with kernels.CONV1X1_STAGED on and the same launch with it off.  Before that each case
-asks the library (kernels.conv1x1_staged_takes -> tdr_conv1x1_bx3_staged_takes) whether the launch is routed to the staged kernel, so no
-case can pass by comparing the generic kernel with itself, and the decline cases assert the opposite.  One eligible shape is also pinned
-on its own against float64 with the single-product probe (tests/_split_probe.py): six products, bar 2^-21.
+weight fragments, same products per 16-channel group in the same order (six, three, one), same accumulators and epilogues -- so every
+case asserts BIT equality (torch.equal) between the launch with kernels.CONV1X1_STAGED on and the same launch with it off.  Before that
+each case asks the library (kernels.conv1x1_staged_takes -> tdr_conv1x1_bx3_staged_takes) whether the launch is routed to the staged
+kernel, so no case can pass by comparing the generic kernel with itself, and the decline cases assert the opposite.  One eligible shape
+of bx3 and one of hx2 are also pinned on their own against float64 with the single-product probe (tests/_split_probe.py): six products,
+bar 2^-21; three products, bar 2^-20.
 
-Every tile configuration the heuristic can pick has its own case (test_every_tile_configuration): a forced configuration stays on the
-generic kernel, so the tile is chosen by the shape -- stage length, octets per stage and quads per tile differ between them (32 channels
-of 128 pixels, 64 of 64, 16 of 256).
+Every tile configuration the heuristic can pick has its own case (test_every_tile_configuration, test_hx2_every_tile_configuration): a
+forced configuration stays on the generic kernel, so the tile is chosen by the shape -- stage length, octets per stage and quads per tile
+differ between them (bx3: 32 channels of 128 pixels, 64 of 64, 16 of 256; hx2 / h1: twice that).
 
-Shapes: the smallest at which the staging can go wrong -- a 128-pixel tile stages 32 channels at a time (half an octet x four pixels
+Shapes: the smallest at which the staging can go wrong.  bx3: a 128-pixel tile stages 32 channels at a time (half an octet x four pixels
 per thread), so Cin = 200 has a partial octet, a partial 16-channel group and a partial last stage; 12 x 12 pixels leave quads wholly
-outside a tile; Cin = 96 is one stage short of the four the dispatch asks for."""
+outside a tile; Cin = 96 is one stage short of the four the dispatch asks for.  hx2 / h1: a 128-pixel tile stages 64 channels (an octet
+x four pixels per thread), so four stages need Cin >= 193: Cin = 200 again has the partial octet, group and last stage, Cin = 192 is one
+stage short, and a launch of more than 512 workgroups stays on the generic kernel.
+
+The fixture K sets the arithmetic: bx3 unless a case asks for another (@MATH('hx2'))."""
 import pytest
 import torch
 
@@ -22,18 +27,22 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture
-def K():
+def K(request):
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
     from textualdegremoval_amd import kernels
     prev_math, prev_switch = kernels.MATH, kernels.CONV1X1_STAGED
-    kernels.set_math('bx3')
+    kernels.set_math(getattr(request, 'param', 'bx3'))
     kernels.CONV1X1_STAGED = True
     try:
         yield kernels
     finally:
         kernels.set_math(prev_math)
         kernels.CONV1X1_STAGED = prev_switch
+
+
+def MATH(mode):
+    return pytest.mark.parametrize('K', [mode], indirect=True)
 
 
 def rnd(*shape, seed, scale=1.0):
@@ -173,5 +182,80 @@ def test_single_product_probe_against_float64(K):
     assert tuple(out.shape) == tuple(exp.shape)
     assert SP.zeros_exact(out, mask), 'an output without a non-zero term is not exactly 0.0'
     worst = SP.max_rel(out, exp, mask)
-    print(f'probe conv1x1_bx3s {N}x{Cin}x{Cout}x{H}x{W} bx3: max rel {worst:.2e} (bar {SP.BAR["bx3"]:.2e})')
+    print(f'probe conv1x1_staged {N}x{Cin}x{Cout}x{H}x{W} bx3: max rel {worst:.2e} (bar {SP.BAR["bx3"]:.2e})')
     assert worst <= SP.BAR['bx3'], (worst, SP.BAR['bx3'])
+
+
+# ---- hx2 / h1: the same kernel with whole-octet tasks, 64-channel stages at a 128-pixel tile, two planes / one
+
+@MATH('hx2')
+def test_hx2_ragged_k(K):
+    """N = 2, 200 -> 96, 8 x 16: four 64-channel stages with a partial last one, a partial octet, a partial group; one 128-pixel tile"""
+    wp, mp = fwd_pack(K, 96, 200, seed=41)
+    both(K, True, rnd(2, 200, 8, 16, seed=42), wp, mp, 96)
+
+
+@MATH('hx2')
+def test_hx2_ragged_pixels_odd_batch(K):
+    """N = 3, 264 -> 160, 12 x 12: five stages, a partial second pixel tile, quads wholly inside or outside, a grid that is no multiple of 8"""
+    wp, mp = fwd_pack(K, 160, 264, seed=43)
+    both(K, True, rnd(3, 264, 12, 12, seed=44), wp, mp, 160)
+
+
+@MATH('hx2')
+def test_hx2_gate_and_kscale(K):
+    """the operand x[:, :200] * x[:, 200:] * kscale[n, c], formed while staging: the gated kernel has ONE register set of operand loads"""
+    wp, mp = fwd_pack(K, 72, 200, seed=45)
+    both(K, True, rnd(2, 400, 8, 16, seed=46), wp, mp, 72, gate=True, kscale=rnd(2, 200, seed=47))
+
+
+# N, Cin, Cout, H, W as TILE_CASES; hx2 stages are twice as long, so Cin is the smallest ragged one with four of them
+HX2_TILE_CASES = {
+    '128x128': (4, 256, 512, 64, 64),      # 64-channel stages; exactly the 512 workgroups of the cap
+    '256x64': (4, 1003, 1024, 32, 32),     # 128-channel stages, eight of them, ragged Cin
+    '32x256': (8, 100, 32, 128, 128),      # 32-channel stages, four of them, ragged Cin; 512 workgroups
+    '32x128': (2, 200, 24, 16, 16),        # 64-channel stages
+    '64x256': (8, 100, 48, 128, 128),      # 32-channel stages, rows past Cout; 512 workgroups
+    '64x128': (2, 200, 96, 8, 16),
+}
+
+
+@MATH('hx2')
+@pytest.mark.parametrize('tile', list(HX2_TILE_CASES))
+def test_hx2_every_tile_configuration(K, tile):
+    N, Cin, Cout, H, W = HX2_TILE_CASES[tile]
+    wp, mp = fwd_pack(K, Cout, Cin, seed=51)
+    both(K, True, rnd(N, Cin, H, W, seed=52), wp, mp, Cout, bias=rnd(Cout, seed=53))
+
+
+@MATH('hx2')
+def test_hx2_declined_launches_stay_on_the_generic_kernel(K):
+    wp, mp = fwd_pack(K, 96, 264, seed=55)
+    both(K, False, rnd(2, 264, 8, 10, seed=56), wp, mp, 96)         # W = 10: no aligned pixel quads
+    wp, mp = fwd_pack(K, 96, 192, seed=57)
+    both(K, False, rnd(2, 192, 8, 16, seed=58), wp, mp, 96)         # three 64-channel stages: one short of four
+    wp, mp = fwd_pack(K, 512, 256, seed=59)
+    both(K, False, rnd(5, 256, 64, 64, seed=60), wp, mp, 512)       # 640 workgroups of 128 x 128: over the cap of 512 (N = 4 is taken, above)
+
+
+@MATH('h1')
+def test_h1_ragged_k(K):
+    """the one-plane form of the same kernel (an hx2 pack's head plane, one product): N = 2, 200 -> 96, 8 x 16"""
+    wp, mp = fwd_pack(K, 96, 200, seed=61)
+    both(K, True, rnd(2, 200, 8, 16, seed=62), wp, mp, 96)
+
+
+@MATH('hx2')
+def test_hx2_single_product_probe_against_float64(K):
+    """one-hot operands: every output is ONE product a * b, so the staged kernel's own product list is pinned at the hx2 bar"""
+    N, Cin, Cout, H, W = 2, 200, 96, 16, 16
+    (x, w), exp, mask = SP.build_conv(N, Cin, Cout, H, W, 1, seed=3)
+    wp, mp, *_ = K.pack_weights(w.cuda().contiguous(), K.PACK_FWD)
+    xd = x.cuda().contiguous()
+    assert K.conv1x1_staged_takes(xd, wp, mp, Cout, 1)
+    out = K.conv_forward(xd, wp, mp, Cout, 1)
+    assert tuple(out.shape) == tuple(exp.shape)
+    assert SP.zeros_exact(out, mask), 'an output without a non-zero term is not exactly 0.0'
+    worst = SP.max_rel(out, exp, mask)
+    print(f'probe conv1x1_staged {N}x{Cin}x{Cout}x{H}x{W} hx2: max rel {worst:.2e} (bar {SP.BAR["hx2"]:.2e})')
+    assert worst <= SP.BAR['hx2'], (worst, SP.BAR['hx2'])

@@ -44,6 +44,16 @@ static inline const char* tdr_tune_env(const char* name) { return getenv(name); 
 static inline const char* tdr_tune_env(const char*) { return nullptr; }
 #endif
 
+// XCD-aware block order of the tiled convolution kernels (workgroup b runs on XCD b % 8, each XCD has its own L2): XCD k walks a
+// contiguous range of the logical (pixel tile, m-tile) sequence with the m-tiles of one pixel tile back to back, so an input tile is
+// fetched from HBM once per XCD and re-used from its L2 by the other m-tiles, and halo lines are shared between neighbouring pixel tiles
+// on the same XCD.  Bijective for any grid size; speed only.  -> the logical index of this workgroup in a grid of gridDim.x
+__device__ __forceinline__ int tdr_xcd_logical_block() {
+    const int T = gridDim.x, b = blockIdx.x;
+    const int q = T >> 3, r = T & 7, xcd = b & 7, slot = b >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+}
+
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 

@@ -22,12 +22,11 @@
 // LDS is double buffered: the global loads of group c+1 are in flight under the MFMAs of group c,
 // one barrier per group.
 #include <stdlib.h>
+#include <type_traits>
 #include "tdr_common.h"
 #include "tdr_conv_epi.h"
 #include "tdr_pack.h"
 #include "../../include/tdr.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // (the ablation / timeline probe variants of round 1 -- profiles/README.md -- were built from this file at commit 7d0042b;
 // the product source carries no probe code)
@@ -42,20 +41,6 @@ constexpr int bx_max_plane(int NT, int KH, int S) {
     return bx_cmax(bx_plane(NT, 8, KH, S), bx_cmax(bx_plane(NT, 16, KH, S), bx_plane(NT, 32, KH, S)));
 }
 
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
-}
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-union Frag {
-    uint4 u;
-    bf16x8 v;
-    f16x8 hv;
-};
-
 // Operand split schemes (fp32 tensors in, fp32 accumulation, fp32-class products):
 //   SCH_BX3  x = h + m + l, bf16 each: 6 cross products (lh, hl, mm, mh, hm, hh) -- any fp32 range
 //   SCH_HX2  x = h + m, fp16 each (11 + 11 mantissa bits): 3 cross products (mh, hm, hh; m*m is 2^-22 relative and
@@ -65,6 +50,9 @@ union Frag {
 //   SCH_H1   x ~ h, one fp16 plane, one product (plain fp16 MFMA, fp32 accumulate): reads the head plane of an hx2 weight pack.
 //            Reduced precision (2^-11 per operand) -- BASELINE configs[4]'s "fp16 MFMA" arithmetic, selected by TDR_MATH=h1 only.
 enum { SCH_BX3 = 0, SCH_HX2 = 1, SCH_H1 = 2 };
+// the products of a 16-channel group as (plane of A, plane of B), small cross terms first, the dominant h*h last
+constexpr int SA[6] = {2, 0, 1, 1, 0, 0}, SB[6] = {0, 2, 1, 0, 1, 0};          // bx3: lh hl mm mh hm hh
+constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 1, 0};                            // hx2: mh hm hh
 
 // Occupancy: the high-resolution 3x3 launches (C = 32 level: 32 x 256 tiles, 21 KB of LDS) are latency-bound -- SQ counters show their
 // waves waiting 55 % of the resident time with 3 waves per SIMD, the occupancy 148 VGPRs allow; asking for 4 (5) resident workgroups
@@ -104,16 +92,7 @@ __global__ __launch_bounds__(256, (KH == 3 && S == 1 && WM == 1 && TM == 1 && TN
     const int TW = 1 << a.tw_log2, SR = 32 >> a.tw_log2, TH = NT * SR;
     const int LH = (TH - 1) * S + KH, LW = (TW - 1) * S + KH;
     const int plane = LH * LW;
-    // XCD-aware block order (workgroup b runs on XCD b % 8, each XCD has its own L2): XCD k walks a contiguous
-    // range of the logical (pixel tile, m-tile) sequence with the m-tiles of one pixel tile back to back, so an
-    // input tile is fetched from HBM once per XCD and re-used from its L2 by the other m-tiles, and halo lines
-    // are shared between neighbouring pixel tiles on the same XCD.  Bijective for any grid size; speed only.
-    int logical;
-    {
-        const int T = gridDim.x, b = blockIdx.x;
-        const int q = T >> 3, r = T & 7, xcd = b & 7, slot = b >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    const int logical = tdr_xcd_logical_block();
     const int mtile = logical % a.mtiles, ptile = logical / a.mtiles;
     const int tx = ptile % a.tiles_x, ty = ptile / a.tiles_x;
     const int m0 = mtile * BM;
@@ -163,7 +142,7 @@ __global__ __launch_bounds__(256, (KH == 3 && S == 1 && WM == 1 && TM == 1 && TN
         const int cbase = g * 16 + sg * 8;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            Frag h, m, l;
+            TdrFrag h, m, l;
             const bool ok = (okmask >> it) & 1u;
             float vv[8];
 #pragma unroll
@@ -191,7 +170,7 @@ __global__ __launch_bounds__(256, (KH == 3 && S == 1 && WM == 1 && TM == 1 && TN
                         h.hv[i] = (_Float16)v;
                     } else {
                         __bf16 hh, mm, ll;
-                        split3(v, hh, mm, ll);
+                        tdr_split3(v, hh, mm, ll);
                         h.v[i] = hh; m.v[i] = mm; l.v[i] = ll;
                     }
                 }
@@ -231,9 +210,9 @@ __global__ __launch_bounds__(256, (KH == 3 && S == 1 && WM == 1 && TM == 1 && TN
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
-    Frag af[TM][NS], afn[TM][NS];
-    Frag aq[AD > 0 ? AD : 1][TM][NS];
-    auto load_a = [&](Frag (&dst)[TM][NS], long gt) {
+    TdrFrag af[TM][NS], afn[TM][NS];
+    TdrFrag aq[AD > 0 ? AD : 1][TM][NS];
+    auto load_a = [&](TdrFrag (&dst)[TM][NS], long gt) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -279,16 +258,14 @@ __global__ __launch_bounds__(256, (KH == 3 && S == 1 && WM == 1 && TM == 1 && TN
                     // (the last prefetch of the last group re-reads a valid slot)
                     const long gtn = min((long)g * TAPS + tap + 1, (long)ngroups * TAPS - 1);
                     if (AD == 0) load_a(afn, gtn);
-                    Frag (&afc)[TM][NS] = AD > 0 ? aq[AD > 0 ? tap % (AD > 0 ? AD : 1) : 0] : af;
+                    TdrFrag (&afc)[TM][NS] = AD > 0 ? aq[AD > 0 ? tap % (AD > 0 ? AD : 1) : 0] : af;
                     if (PF > 1 && tap == 0 && g + PF < ngroups) load_group(g + PF, u);   // set u is free: group g already sits in LDS
-                    Frag bf[TN][NS];
+                    TdrFrag bf[TN][NS];
 #pragma unroll
                     for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
                         for (int s = 0; s < NS; ++s) bf[tn][s].u = sb[s * 2 * plane + bbase[tn] + tapoff];
-                    // small cross terms first, the dominant h*h last
-                    constexpr int SA[6] = {2, 0, 1, 1, 0, 0}, SB[6] = {0, 2, 1, 0, 1, 0};          // bx3: lh hl mm mh hm hh
-                    constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 1, 0};                            // hx2: mh hm hh
+                    // small cross terms first, the dominant h*h last (SA / SB, HA / HB)
 #pragma unroll
                     for (int q = 0; q < NP; ++q)
 #pragma unroll
@@ -331,30 +308,53 @@ __global__ __launch_bounds__(256, (KH == 3 && S == 1 && WM == 1 && TM == 1 && TN
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// 1x1 / stride 1 / 2-way fp16 split with 16-byte operand staging.
+// 1x1 / stride 1 with 16-byte operand loads, every split scheme.
 //
 // The generic kernel above stages pixels with one dword load per (lane, channel): on the K <= 256 layers the texture-
 // address path, not the matrix pipe, is the limit (profiles/README.md, timeline probe).  A 1x1 tile has no halo, so here a
-// lane owns 4 adjacent pixels x 8 channels = eight float4 loads (128-byte row segments per 8 lanes), converts them to the
-// same [split][octet][pixel] 16-byte LDS slots, and one pass of the 256 threads stages KS = 8192 / NPX channels (64 for
-// a 128-pixel tile) instead of 16: a quarter of the vector-memory instructions and a quarter of the barriers.  LDS slots
-// are XOR-swizzled (slot ^ ((slot >> 4) & 3)) so that both the 4-slot-strided writes and the 32-contiguous fragment reads
-// are conflict-free.  Same weight fragments, accumulator layout and epilogues as conv_bx3_kernel.
+// thread owns 4 adjacent pixels x CPT channels = CPT float4 loads (128-byte row segments per 8 lanes), splits them in
+// registers exactly as store_group does (same pins: every plane from one fp32 value) into the same [plane][octet][pixel]
+// 16-byte LDS slots, and one pass of the 256 threads stages KS channels instead of 16.  LDS slots are XOR-swizzled
+// (slot ^ ((slot >> 4) & 3)) so that both the 4-slot-strided writes and the 32-contiguous fragment reads are conflict-free.
+// Same weight fragments, same products per 16-channel group in the same order into the same accumulators and the same
+// epilogues as conv_bx3_kernel<1, 1, ...>: the output is bit-identical to the generic kernel at the same tile
+// configuration.  Only the staging differs.
+//   hx2 / h1: a thread takes a whole octet (CPT = 8) and writes whole slots: KS = 8192 / NPX channels (64 for a 128-pixel
+//        tile), a quarter of the vector-memory instructions and a quarter of the barriers; a stage is 32 KiB (h1: 16 KiB).
+//   bx3: three planes of a stage must fit twice into 64 KiB (two workgroups per CU, double buffered), so a stage is 24 KiB:
+//        512 slots = KS x NPX / 8, i.e. KS = 4096 / NPX channels (32 for a 128-pixel tile, 64 for 64 pixels, 16 for 256).
+//        That is half a (octet, quad) task per thread, and every thread takes half an octet (CPT = 4), written as the 8-byte
+//        halves of the 16-byte slots (twelve ds_write_b64 per stage; per 32 channels the generic pipeline issues 16 dword
+//        loads, six ds_write_b128 and two barriers per thread, this one 4 loads, 12 half-slot writes and one barrier).
+// Operand loads run PFD stages ahead in PFD register sets: two, or one for the gated hx2 / h1 operand (16 float4 a set).
 // ---------------------------------------------------------------------------------------------------------------
+template <int WM, int TN, int SCH>
+struct C1Stage {
+    static constexpr int NS = SCH == SCH_BX3 ? 3 : (SCH == SCH_HX2 ? 2 : 1);   // operand planes (LDS, fragments)
+    static constexpr int NSW = SCH == SCH_BX3 ? 3 : 2;                         // planes of the weight pack
+    static constexpr int NP = SCH == SCH_BX3 ? 6 : (SCH == SCH_HX2 ? 3 : 1);   // matrix products per fp32 product
+    static constexpr int NPX = 32 * TN * (4 / WM);     // pixels per tile
+    static constexpr int QUADS = NPX / 4;              // float4 pixel quads per tile
+    static constexpr int CPT = SCH == SCH_BX3 ? 4 : 8; // channels per thread: half an octet or a whole one
+    static constexpr int KS = CPT * 256 / QUADS;       // channels per stage: one (CPT channels, quad) task per thread
+    static constexpr int OCT = KS / 8;                 // octets per stage
+    static constexpr int GPS = KS / 16;                // 16-channel MFMA groups per stage
+    static constexpr int BYTES = NS * OCT * NPX * 16;  // one stage in LDS
+    static_assert(GPS >= 1 && (SCH != SCH_BX3 || BYTES == 24576), "a bx3 stage is 24 KiB");
+    static_assert(SCH != SCH_HX2 || BYTES == 32768, "an hx2 stage is 32 KiB");
+};
+
 __device__ __forceinline__ int swz1(int slot) { return slot ^ ((slot >> 4) & 3); }
 
-template <int WM, int TM, int TN, int EPI, bool GATE, int SCH = SCH_HX2>
-__global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
-    constexpr int NS = SCH == SCH_H1 ? 1 : 2, NSW = 2, NP = SCH == SCH_H1 ? 1 : 3;
+template <int WM, int TM, int TN, int EPI, bool GATE, int SCH>
+__global__ __launch_bounds__(256, 2) void conv1x1_staged_kernel(ConvArgs a) {
+    using T = C1Stage<WM, TN, SCH>;
+    constexpr int NS = T::NS, NSW = T::NSW, NP = T::NP, NPX = T::NPX, QUADS = T::QUADS, CPT = T::CPT, KS = T::KS, GPS = T::GPS;
     constexpr int WN = 4 / WM;
     constexpr int BM = 32 * TM * WM;
     constexpr int NT = TN * WN;
-    constexpr int NPX = 32 * NT;          // pixels per tile
-    constexpr int QUADS = NPX / 4;        // float4 pixel quads per tile
-    constexpr int OCT = 256 / QUADS;      // 8-channel octets staged per pass: one (octet, quad) task per thread
-    constexpr int KS = 8 * OCT;           // channels per stage
-    constexpr int GPS = KS / 16;          // 16-channel MFMA groups per stage
-    constexpr int PFD = GATE ? 1 : 2;     // stages of operand loads in flight (register sets)
+    constexpr int PL = T::OCT * NPX;                          // 16-byte slots per plane of a stage
+    constexpr int PFD = (GATE && SCH != SCH_BX3) ? 1 : 2;     // stages of operand loads in flight (register sets)
 
     extern __shared__ __attribute__((aligned(16))) uint4 smem4[];
 
@@ -362,12 +362,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
     const int wm = wave / WN, wn = wave % WN;
     const int j = lane & 31, kk = lane >> 5;
     const int TW = 1 << a.tw_log2, SR = 32 >> a.tw_log2, TH = NT * SR;
-    int logical;
-    {   // XCD-aware block order, as in conv_bx3_kernel
-        const int T = gridDim.x, b = blockIdx.x;
-        const int q = T >> 3, r = T & 7, xcd = b & 7, slot = b >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    const int logical = tdr_xcd_logical_block();
     const int mtile = logical % a.mtiles, ptile = logical / a.mtiles;
     const int tx = ptile % a.tiles_x, ty = ptile / a.tiles_x;
     const int m0 = mtile * BM;
@@ -375,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
     const int oy0 = ty * TH, ox0 = tx * TW;
     const long HWin = (long)a.H * a.W;
 
-    // ---- staging task of this thread: octet so, pixel quad sq
+    // ---- staging task of this thread: channels CPT so .. CPT so + CPT - 1 of the stage, pixel quad sq
     const int so = tid / QUADS, sq = tid % QUADS;
     const int p0 = 4 * sq;
     const int gy = oy0 + (p0 >> a.tw_log2), gx = ox0 + (p0 & (TW - 1));
@@ -386,15 +381,15 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
     const int ngroups = (a.Cin + 15) >> 4;
     const int nstages = (a.Cin + KS - 1) / KS;
 
-    float4 rin[PFD][8];
-    float4 rin2[GATE ? PFD : 1][GATE ? 8 : 1];
-    float rks[PFD][8];
+    float4 rin[PFD][CPT];
+    float4 rin2[GATE ? PFD : 1][GATE ? CPT : 1];
+    float rks[PFD][CPT];
     auto load_stage = [&](int st, int set) {
-        const int cbase = st * KS + so * 8;
+        const int cbase = st * KS + so * CPT;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < CPT; ++i) {
             const int ci = cbase + i;
-            rin[set][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            rin[set][i] = make_float4(0.f, 0.f, 0.f, 0.f);      // outside the image / past Cin: exact zeros in every plane
             rks[set][i] = 1.f;
             if (GATE) rin2[set][i] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (pok && ci < a.Cin) {
@@ -405,37 +400,45 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
             }
         }
     };
-    int wslot[4];
+    int wslot[4];                                     // CPT == 8: 16-byte slots; CPT == 4: 8-byte units (16-byte slot, half so & 1)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) wslot[i] = so * NPX + swz1(p0 + i);
+    for (int i = 0; i < 4; ++i) wslot[i] = CPT == 8 ? so * NPX + swz1(p0 + i) : 2 * ((so >> 1) * NPX + swz1(p0 + i)) + (so & 1);
+    union HalfFrag { uint2 u; __bf16 v[4]; };                      // (an array: as half a bf16x8 vector the splits are packed differently)
+    using Slot = std::conditional_t<CPT == 8, uint4, uint2>;       // what a thread writes per (plane, pixel)
     auto store_stage = [&](int set, int buf) {
-        uint4* sb = smem4 + buf * (NS * OCT * NPX);
+        Slot* sb = reinterpret_cast<Slot*>(smem4 + buf * (NS * PL));
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
-            Frag h, m;
-            float vv[8];
+            std::conditional_t<CPT == 8, TdrFrag, HalfFrag> f[NS];
+            [[maybe_unused]] float vv[CPT];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
+            for (int i = 0; i < CPT; ++i) {
                 const float4 q4 = rin[set][i];
                 float v = px == 0 ? q4.x : (px == 1 ? q4.y : (px == 2 ? q4.z : q4.w));
                 if (GATE) {
                     const float4 g4 = rin2[set][i];
                     v *= px == 0 ? g4.x : (px == 1 ? g4.y : (px == 2 ? g4.z : g4.w));
                 }
-                vv[i] = v * rks[set][i];
+                v *= rks[set][i];
+                if constexpr (SCH == SCH_BX3) {
+                    asm volatile("" : "+v"(v));            // pin: every split plane from the same fp32 value (conv_bx3_kernel)
+                    __bf16 hh, mm, ll;
+                    tdr_split3(v, hh, mm, ll);
+                    f[0].v[i] = hh; f[1].v[i] = mm; f[2].v[i] = ll;
+                } else {
+                    vv[i] = v;
+                }
             }
-            if constexpr (NS == 2) {
-                unsigned hd[4], md[4];                    // one fp32 value for head and residual (see conv_bx3_kernel)
+            if constexpr (SCH == SCH_HX2) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) tdr_split2_f16(vv[2 * i], vv[2 * i + 1], hd[i], md[i]);
-                h.u = make_uint4(hd[0], hd[1], hd[2], hd[3]);
-                m.u = make_uint4(md[0], md[1], md[2], md[3]);
-            } else {
+                for (int i = 0; i < CPT / 2; ++i)          // one fp32 value for head and residual (see conv_bx3_kernel)
+                    tdr_split2_f16(vv[2 * i], vv[2 * i + 1], f[0].d[i], f[1].d[i]);
+            } else if constexpr (SCH == SCH_H1) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) h.hv[i] = (_Float16)vv[i];
+                for (int i = 0; i < CPT; ++i) f[0].hv[i] = (_Float16)vv[i];
             }
-            sb[wslot[px]] = h.u;
-            if constexpr (NS == 2) sb[OCT * NPX + wslot[px]] = m.u;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) sb[s * (PL * 16 / (int)sizeof(Slot)) + wslot[px]] = f[s].u;
         }
     };
 
@@ -460,8 +463,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
-    Frag af[TM][NS], afn[TM][NS];
-    auto load_a = [&](Frag (&dst)[TM][NS], long g) {
+    TdrFrag af[TM][NS], afn[TM][NS];
+    auto load_a = [&](TdrFrag (&dst)[TM][NS], long g) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -481,7 +484,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
             const int st = s0 + u;
             if (st < nstages) {
                 const int buf = st & 1;
-                const uint4* sb = smem4 + buf * (NS * OCT * NPX);
+                const uint4* sb = smem4 + buf * (NS * PL);
 #pragma unroll
                 for (int gg = 0; gg < GPS; ++gg) {
                     const int g = st * GPS + gg;
@@ -490,12 +493,11 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
                         // set u is free (stage st already sits in LDS): the loads of stage st + PFD go out behind the
                         // first weight-fragment prefetch, so the in-order wait for the fragments leaves them in flight
                         if (gg == 0 && st + PFD < nstages) load_stage(st + PFD, u);
-                        Frag bf[TN][NS];
+                        TdrFrag bf[TN][NS];
 #pragma unroll
                         for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
-                            for (int s = 0; s < NS; ++s) bf[tn][s].u = sb[s * (OCT * NPX) + 2 * gg * NPX + bslot[tn]];
-                        constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 1, 0};   // mh hm hh
+                            for (int s = 0; s < NS; ++s) bf[tn][s].u = sb[s * PL + 2 * gg * NPX + bslot[tn]];
 #pragma unroll
                         for (int q = 0; q < NP; ++q)
 #pragma unroll
@@ -504,8 +506,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
                                 for (int tn = 0; tn < TN; ++tn) {
                                     if constexpr (SCH == SCH_H1)
                                         acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[tm][0].hv, bf[tn][0].hv, acc[tm][tn], 0, 0, 0);
-                                    else
+                                    else if constexpr (SCH == SCH_HX2)
                                         acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[tm][HA[q]].hv, bf[tn][HB[q]].hv, acc[tm][tn], 0, 0, 0);
+                                    else
+                                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[tm][SA[q]].v, bf[tn][SB[q]].v, acc[tm][tn], 0, 0, 0);
                                 }
 #pragma unroll
                         for (int tm = 0; tm < TM; ++tm)
@@ -528,286 +532,88 @@ __global__ __launch_bounds__(256, 2) void conv1x1_hx2_kernel(ConvArgs a) {
     conv_epilogue<TM, TN, EPI>(a, acc, n, m0, wm, wn, oy0, ox0, j, kk);
 }
 
-template <int WM, int TM, int TN, int EPI, bool GATE, int SCH>
-int launch_c1_hx2(const ConvArgs& a, int N, hipStream_t st) {
-    constexpr int WN = 4 / WM;
-    constexpr int BM = 32 * TM * WM;
-    constexpr int NT = TN * WN;
-    const int TW = 1 << a.tw_log2, SR = 32 >> a.tw_log2, TH = NT * SR;
-    ConvArgs b = a;
-    b.tiles_x = tdr_cdiv(a.OW, TW);
-    const int tiles_y = tdr_cdiv(a.OH, TH);
-    b.mtiles = tdr_cdiv(a.Cout, BM);
-    dim3 grid(b.tiles_x * tiles_y * b.mtiles, 1, N);
-    b.single_buf = 0;
-    const size_t lds = 2 * 32768;        // two stages of 2 splits x OCT octets x NPX pixels x 16 B = 32 KiB
-    auto kern = conv1x1_hx2_kernel<WM, TM, TN, EPI, GATE, SCH>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, b);
-    TDR_LAUNCH_CHECK("conv1x1_hx2_kernel");
-    return TDR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// 1x1 / stride 1 / 3-way bf16 split (the default arithmetic) with 16-byte operand loads.
-//
-// The float4-staged form of conv_bx3_kernel<1, 1, ..., SCH_BX3>: same weight fragments, same [plane][octet][pixel] LDS slots
-// (XOR-swizzled as above), same six products per 16-channel group in the same order into the same accumulators, same
-// epilogues -- the output is bit-identical to the generic kernel at the same tile configuration.  Only the staging differs.
-// Three planes of a stage must fit twice into 64 KiB (two workgroups per CU, double buffered), so a stage is 24 KiB:
-// 512 slots = KS x NPX / 8, i.e. KS = 4096 / NPX channels (32 for a 128-pixel tile, 64 for 64 pixels, 16 for 256).  That is
-// half a (octet, quad) task per thread, and every thread takes half an octet: 4 channels x 4 adjacent pixels = four float4
-// loads, split in registers exactly as store_group does (same pin: every plane from one fp32 value), written as the 8-byte
-// halves of the 16-byte slots (twelve ds_write_b64 per stage; per 32 channels the generic pipeline issues 16 dword loads,
-// six ds_write_b128 and two barriers per thread, this one 4 loads, 12 half-slot writes and one barrier).  Operand loads run
-// two stages ahead in two register sets.
-// ---------------------------------------------------------------------------------------------------------------
-template <int WM, int TM, int TN, int EPI, bool GATE>
-__global__ __launch_bounds__(256, 2) void conv1x1_bx3s_kernel(ConvArgs a) {
-    constexpr int NS = 3, NP = 6;
-    constexpr int WN = 4 / WM;
-    constexpr int BM = 32 * TM * WM;
-    constexpr int NT = TN * WN;
-    constexpr int NPX = 32 * NT;          // pixels per tile
-    constexpr int QUADS = NPX / 4;        // float4 pixel quads per tile
-    constexpr int HOCT = 256 / QUADS;     // 4-channel half octets staged per pass: one (half octet, quad) task per thread
-    constexpr int KS = 4 * HOCT;          // channels per stage
-    constexpr int OCT = KS / 8;           // octets per stage
-    constexpr int GPS = KS / 16;          // 16-channel MFMA groups per stage
-    constexpr int PFD = 2;                // stages of operand loads in flight (register sets)
-    static_assert(GPS >= 1 && NS * OCT * NPX * 16 == 24576, "a stage is 24 KiB");
-
-    extern __shared__ __attribute__((aligned(16))) uint4 smem4[];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int j = lane & 31, kk = lane >> 5;
-    const int TW = 1 << a.tw_log2, SR = 32 >> a.tw_log2, TH = NT * SR;
-    int logical;
-    {   // XCD-aware block order, as in conv_bx3_kernel
-        const int T = gridDim.x, b = blockIdx.x;
-        const int q = T >> 3, r = T & 7, xcd = b & 7, slot = b >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
-    const int mtile = logical % a.mtiles, ptile = logical / a.mtiles;
-    const int tx = ptile % a.tiles_x, ty = ptile / a.tiles_x;
-    const int m0 = mtile * BM;
-    const int n = blockIdx.z;
-    const int oy0 = ty * TH, ox0 = tx * TW;
-    const long HWin = (long)a.H * a.W;
-
-    // ---- staging task of this thread: half octet sh (channels 4 sh .. 4 sh + 3 of the stage), pixel quad sq
-    const int sh = tid / QUADS, sq = tid % QUADS;
-    const int p0 = 4 * sq;
-    const int gy = oy0 + (p0 >> a.tw_log2), gx = ox0 + (p0 & (TW - 1));
-    const bool pok = gy < a.H && gx < a.W;            // W % 4 == 0: a quad is inside or outside as a whole
-    const long goff = pok ? (long)gy * a.W + gx : 0;
-    const float* in_n = a.in + (long)n * a.in_ns;
-    const float* ks_n = a.kscale ? a.kscale + (long)n * a.kscale_ns : nullptr;
-    const int ngroups = (a.Cin + 15) >> 4;
-    const int nstages = (a.Cin + KS - 1) / KS;
-
-    float4 rin[PFD][4];
-    float4 rin2[GATE ? PFD : 1][GATE ? 4 : 1];
-    float rks[PFD][4];
-    auto load_stage = [&](int st, int set) {
-        const int cbase = st * KS + sh * 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int ci = cbase + i;
-            rin[set][i] = make_float4(0.f, 0.f, 0.f, 0.f);      // outside the image / past Cin: exact zeros in every plane
-            rks[set][i] = 1.f;
-            if (GATE) rin2[set][i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (pok && ci < a.Cin) {
-                const float* src = in_n + (long)ci * HWin + goff;
-                rin[set][i] = *reinterpret_cast<const float4*>(src);
-                if (GATE) rin2[set][i] = *reinterpret_cast<const float4*>(src + a.gate_off);
-                if (ks_n) rks[set][i] = ks_n[ci];
-            }
-        }
-    };
-    int wslot[4];                                     // in 8-byte units: 16-byte slot, half sh & 1
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wslot[i] = 2 * ((sh >> 1) * NPX + swz1(p0 + i)) + (sh & 1);
-    auto store_stage = [&](int set, int buf) {
-        uint2* sb = reinterpret_cast<uint2*>(smem4 + buf * (NS * OCT * NPX));
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            union { uint2 u; __bf16 v[4]; } h, m, l;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float4 q4 = rin[set][i];
-                float v = px == 0 ? q4.x : (px == 1 ? q4.y : (px == 2 ? q4.z : q4.w));
-                if (GATE) {
-                    const float4 g4 = rin2[set][i];
-                    v *= px == 0 ? g4.x : (px == 1 ? g4.y : (px == 2 ? g4.z : g4.w));
-                }
-                v *= rks[set][i];
-                asm volatile("" : "+v"(v));            // pin: every split plane from the same fp32 value (conv_bx3_kernel)
-                __bf16 hh, mm, ll;
-                split3(v, hh, mm, ll);
-                h.v[i] = hh; m.v[i] = mm; l.v[i] = ll;
-            }
-            sb[wslot[px]] = h.u;
-            sb[2 * (OCT * NPX) + wslot[px]] = m.u;
-            sb[4 * (OCT * NPX) + wslot[px]] = l.u;
-        }
-    };
-
-    // ---- fragment addresses
-    int bslot[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) bslot[tn] = kk * NPX + swz1(32 * (wn * TN + tn) + j);
-    const int MT = a.Mpad >> 5;
-    const uint4* wfrag[TM];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-        const int mt = min((m0 >> 5) + wm * TM + tm, MT - 1);
-        wfrag[tm] = reinterpret_cast<const uint4*>(a.wp) + (long)n * (a.wp_ns >> 2) + (long)mt * (NS * 64) + lane;
-    }
-    const long wstep = (long)MT * (NS * 64);
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
-
-    Frag af[TM][NS], afn[TM][NS];
-    auto load_a = [&](Frag (&dst)[TM][NS], long g) {
-#pragma unroll
-        for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-            for (int s = 0; s < NS; ++s) dst[tm][s].u = wfrag[tm][g * wstep + s * 64];
-    };
-
-    load_a(af, 0);
-#pragma unroll
-    for (int p = 0; p < PFD; ++p)
-        if (p < nstages) load_stage(p, p);
-    store_stage(0, 0);
-    __syncthreads();
-
-    for (int s0 = 0; s0 < nstages; s0 += PFD) {
-#pragma unroll
-        for (int u = 0; u < PFD; ++u) {
-            const int st = s0 + u;
-            if (st < nstages) {
-                const int buf = st & 1;
-                const uint4* sb = smem4 + buf * (NS * OCT * NPX);
-#pragma unroll
-                for (int gg = 0; gg < GPS; ++gg) {
-                    const int g = st * GPS + gg;
-                    if (g < ngroups) {
-                        load_a(afn, min(g + 1, ngroups - 1));
-                        // set u is free (stage st already sits in LDS): the loads of stage st + PFD go out behind the
-                        // first weight-fragment prefetch, so the in-order wait for the fragments leaves them in flight
-                        if (gg == 0 && st + PFD < nstages) load_stage(st + PFD, u);
-                        Frag bf[TN][NS];
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                            for (int s = 0; s < NS; ++s) bf[tn][s].u = sb[s * (OCT * NPX) + 2 * gg * NPX + bslot[tn]];
-                        constexpr int SA[6] = {2, 0, 1, 1, 0, 0}, SB[6] = {0, 2, 1, 0, 1, 0};   // lh hl mm mh hm hh (conv_bx3_kernel)
-#pragma unroll
-                        for (int q = 0; q < NP; ++q)
-#pragma unroll
-                            for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                                for (int tn = 0; tn < TN; ++tn)
-                                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[tm][SA[q]].v, bf[tn][SB[q]].v, acc[tm][tn], 0, 0, 0);
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                            for (int s = 0; s < NS; ++s) af[tm][s] = afn[tm][s];
-                    }
-                }
-                if (st + 1 < nstages) store_stage((u + 1) % PFD, buf ^ 1);
-                __syncthreads();
-            }
-        }
-    }
-
-    if constexpr (EPI != EPI_PSHUF) {
-        if (a.vec_epi) {
-            conv_epilogue_vec<TM, TN, EPI>(a, acc, n, m0, wm, wn, oy0, ox0, lane, reinterpret_cast<float*>(smem4) + wave * (32 * 36));
-            return;
-        }
-    }
-    conv_epilogue<TM, TN, EPI>(a, acc, n, m0, wm, wn, oy0, ox0, j, kk);
-}
-
-// 16-byte staging needs whole, aligned pixel quads; it pays from four stages of K on and for launches of a single
-// round of workgroups (probe_conv1x1.py / kernel traces on MI355X: 256->512 @64x64 N=4 30.1 -> 27.0 us, 512->256 37.9
-// -> 32.2 us; 128->256 @256x256 with two stages 123 -> 134 us, 64->128 @512x512 with one stage 189 -> 226 us; 2048
-// workgroups of 256->256 @128x128 87 -> 96 us: with 64 KiB of LDS only two workgroups share a CU, and the many-round
-// launches want the four or five of the 16-channel pipeline of conv_bx3_kernel)
-inline bool c1_hx2_ok(const ConvArgs& a, int npx, int bm, int N) {
-    static const bool off = tdr_tune_env("TDR_C1_OLD") != nullptr;
-    static const int min_stages = tdr_tune_env("TDR_C1_STAGES") ? atoi(tdr_tune_env("TDR_C1_STAGES")) : 4;
-    static const long max_blocks = tdr_tune_env("TDR_C1_BLOCKS") ? atol(tdr_tune_env("TDR_C1_BLOCKS")) : 512;
-    const int ks = 8192 / npx;
-    const long blocks = (long)tdr_cdiv((long)a.OH * a.OW, npx) * tdr_cdiv(a.Cout, bm) * N;
-    return !off && blocks <= max_blocks && (a.Cin + ks - 1) / ks >= min_stages && a.pad == 0 && a.W % 4 == 0 && a.in_ns % 4 == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0 &&
-           a.H == a.OH && a.W == a.OW;
-}
-
-template <int WM, int TM, int TN, int EPI, bool GATE>
-int launch_c1_bx3s(const ConvArgs& a, int N, hipStream_t st) {
-    constexpr int WN = 4 / WM;
-    constexpr int BM = 32 * TM * WM;
-    constexpr int NT = TN * WN;
-    const int TW = 1 << a.tw_log2, SR = 32 >> a.tw_log2, TH = NT * SR;
-    ConvArgs b = a;
-    b.tiles_x = tdr_cdiv(a.OW, TW);
-    const int tiles_y = tdr_cdiv(a.OH, TH);
-    b.mtiles = tdr_cdiv(a.Cout, BM);
-    dim3 grid(b.tiles_x * tiles_y * b.mtiles, 1, N);
-    b.single_buf = 0;
-    const size_t lds = 2 * 24576;        // two stages of 3 planes x 512 slots x 16 B (above the vector epilogue's 18 KiB)
-    hipLaunchKernelGGL((conv1x1_bx3s_kernel<WM, TM, TN, EPI, GATE>), grid, dim3(256), lds, st, b);
-    TDR_LAUNCH_CHECK("conv1x1_bx3s_kernel");
-    return TDR_OK;
-}
-
 // tile-configuration override for profiles/autotune_conv.py: [0] 1x1 kernels, [1] 3x3 / 2x2 kernels; 0 = heuristic
 int g_force_cfg[2] = {tdr_tune_env("TDR_BX_CFG1") ? atoi(tdr_tune_env("TDR_BX_CFG1")) : 0, tdr_tune_env("TDR_BX_CFG3") ? atoi(tdr_tune_env("TDR_BX_CFG3")) : 0};
-int g_c1_bx3_staged = 1;          // tdr_conv1x1_bx3_staged_set: 0 keeps every bx3 1x1 launch on conv_bx3_kernel
-thread_local int* g_c1_bx3_query = nullptr;    // tdr_conv1x1_bx3_staged_takes: the dispatch below, on the asking thread only, records its decision here and launches nothing
+int g_c1_staged = 1;                       // tdr_conv1x1_bx3_staged_set: 0 keeps every 1x1 launch, of any arithmetic, on conv_bx3_kernel
+thread_local int* g_c1_query = nullptr;    // tdr_conv1x1_bx3_staged_takes: the dispatch below, on the asking thread only, records its decision here and launches nothing
 
-// The eligibility rule of c1_hx2_ok with the stage length of the 24 KiB bx3 stage (4096 / npx channels), for the heuristic's own
-// tile configuration only: a forced one (tdr_conv_force_cfg(1, cfg != 0)) names a configuration of conv_bx3_kernel and stays there.
-// No workgroup cap (the hx2 form has one at 512): launches of 1024 - 8192 workgroups measured 7 - 21 % faster than the generic kernel as
-// well, at the same two workgroups per CU (profiles/conv1x1_bx3/README.md; tuning builds: TDR_C1_BLOCKS sets a cap).
-// The 256-pixel tiles (16-channel stages: the generic kernel's barrier count, only the wider loads) measured 3 - 12 % faster and stay in.
-inline bool c1_bx3_ok(const ConvArgs& a, int npx, int bm, int N) {
-    static const long max_blocks = tdr_tune_env("TDR_C1_BLOCKS") ? atol(tdr_tune_env("TDR_C1_BLOCKS")) : (1L << 40);
-    const int ks = 4096 / npx;
+// 16-byte staging needs whole, aligned pixel quads, and it pays from four stages of K on (128->256 @256x256 with two hx2
+// stages 123 -> 134 us, 64->128 @512x512 with one stage 189 -> 226 us).
+//   hx2 / h1 (64 / 32 KiB of LDS): for launches of a single round of workgroups, at most 512 (probe_conv1x1.py / kernel traces on
+//        MI355X: 256->512 @64x64 N=4 30.1 -> 27.0 us, 512->256 37.9 -> 32.2 us; 2048 workgroups of 256->256 @128x128 87 -> 96
+//        us: with 64 KiB of LDS only two workgroups share a CU, and the many-round launches want the four or five of the
+//        16-channel pipeline of conv_bx3_kernel).  Tuning builds: TDR_C1_OLD turns it off, TDR_C1_STAGES sets the stage count.
+//   bx3 (48 KiB): for the heuristic's own tile configuration only -- a forced one (tdr_conv_force_cfg(1, cfg != 0)) names a
+//        configuration of conv_bx3_kernel and stays there.  No workgroup cap: launches of 1024 - 8192 workgroups measured 7 - 21 %
+//        faster than the generic kernel as well, at the same two workgroups per CU (profiles/conv1x1_bx3/README.md).  The
+//        256-pixel tiles (16-channel stages: the generic kernel's barrier count, only the wider loads) measured 3 - 12 %
+//        faster and stay in.
+// Tuning builds: TDR_C1_BLOCKS sets the workgroup cap of either.
+inline long c1_block_cap(long dflt) {
+    static const char* env = tdr_tune_env("TDR_C1_BLOCKS");
+    return env ? atol(env) : dflt;
+}
+
+template <int SCH>
+bool c1_staged_ok(const ConvArgs& a, int npx, int bm, int N) {
+    const long max_blocks = c1_block_cap(SCH == SCH_BX3 ? (1L << 40) : 512);
+    int min_stages = 4;
+    if constexpr (SCH == SCH_BX3) {
+        if (g_force_cfg[0] != 0) return false;
+    } else {
+        static const bool off = tdr_tune_env("TDR_C1_OLD") != nullptr;
+        static const int stages_env = tdr_tune_env("TDR_C1_STAGES") ? atoi(tdr_tune_env("TDR_C1_STAGES")) : 4;
+        if (off) return false;
+        min_stages = stages_env;
+    }
+    const int ks = (SCH == SCH_BX3 ? 4096 : 8192) / npx;      // C1Stage::KS
     const long blocks = (long)tdr_cdiv((long)a.OH * a.OW, npx) * tdr_cdiv(a.Cout, bm) * N;
-    return g_c1_bx3_staged && g_force_cfg[0] == 0 && blocks <= max_blocks && (a.Cin + ks - 1) / ks >= 4 && a.pad == 0 && a.W % 4 == 0 && a.in_ns % 4 == 0 &&
+    return g_c1_staged && blocks <= max_blocks && (a.Cin + ks - 1) / ks >= min_stages && a.pad == 0 && a.W % 4 == 0 && a.in_ns % 4 == 0 &&
            (reinterpret_cast<uintptr_t>(a.in) & 15) == 0 && a.H == a.OH && a.W == a.OW;
+}
+
+// the grid of BM x 32 NT tiles (x: pixel tiles x m-tiles, z: images); fills b.tiles_x / b.mtiles for the kernel's block order
+inline dim3 tile_grid(const ConvArgs& a, int BM, int NT, int N, ConvArgs& b) {
+    const int TW = 1 << a.tw_log2, TH = NT * (32 >> a.tw_log2);
+    b.tiles_x = tdr_cdiv(a.OW, TW);
+    b.mtiles = tdr_cdiv(a.Cout, BM);
+    return dim3(b.tiles_x * tdr_cdiv(a.OH, TH) * b.mtiles, 1, N);
+}
+
+// one launch of KERN; RAISE: lift its dynamic-LDS limit above the default 64 KiB first, once per kernel instantiation
+template <auto KERN, bool RAISE = true>
+int launch_conv(const char* name, dim3 grid, size_t lds, hipStream_t st, const ConvArgs& b) {
+    if constexpr (RAISE) {
+        static bool attr_set = false;
+        if (!attr_set) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            attr_set = true;
+        }
+    }
+    hipLaunchKernelGGL(KERN, grid, dim3(256), lds, st, b);
+    TDR_LAUNCH_CHECK(name);
+    return TDR_OK;
+}
+
+template <int WM, int TM, int TN, int EPI, bool GATE, int SCH>
+int launch_c1_staged(const ConvArgs& a, int N, hipStream_t st) {
+    ConvArgs b = a;
+    const dim3 grid = tile_grid(a, 32 * TM * WM, TN * (4 / WM), N, b);
+    b.single_buf = 0;
+    // two stages: 48 KiB (bx3; above the vector epilogue's 18 KiB), 64 KiB (hx2) or 32 KiB (h1)
+    return launch_conv<conv1x1_staged_kernel<WM, TM, TN, EPI, GATE, SCH>, SCH != SCH_BX3>("conv1x1_staged_kernel", grid, 2 * C1Stage<WM, TN, SCH>::BYTES, st, b);
 }
 
 template <int KH, int S, int WM, int TM, int TN, int EPI, bool GATE, int SCH>
 int launch_bx_cfg_s(const ConvArgs& a, int N, hipStream_t st) {
-    if constexpr (KH == 1 && S == 1 && SCH == SCH_BX3 && EPI != EPI_PSHUF) {
-        const bool staged = c1_bx3_ok(a, 32 * TN * (4 / WM), 32 * TM * WM, N);
-        if (g_c1_bx3_query) { *g_c1_bx3_query = staged ? 1 : 0; return TDR_OK; }
-        if (staged) return launch_c1_bx3s<WM, TM, TN, EPI, GATE>(a, N, st);
+    if constexpr (KH == 1 && S == 1 && EPI != EPI_PSHUF) {
+        const bool staged = c1_staged_ok<SCH>(a, 32 * TN * (4 / WM), 32 * TM * WM, N);
+        if (g_c1_query) { *g_c1_query = staged ? 1 : 0; return TDR_OK; }
+        if (staged) return launch_c1_staged<WM, TM, TN, EPI, GATE, SCH>(a, N, st);
     }
-    if (g_c1_bx3_query) return TDR_OK;    // any other launch: the query's answer stays 0
-    if constexpr (KH == 1 && S == 1 && SCH != SCH_BX3 && EPI != EPI_PSHUF)
-        if (c1_hx2_ok(a, 32 * TN * (4 / WM), 32 * TM * WM, N)) return launch_c1_hx2<WM, TM, TN, EPI, GATE, SCH>(a, N, st);
+    if (g_c1_query) return TDR_OK;    // any other launch: the query's answer stays 0
     constexpr int NS = SCH == SCH_BX3 ? 3 : (SCH == SCH_HX2 ? 2 : 1);
-    constexpr int WN = 4 / WM;
-    constexpr int BM = 32 * TM * WM;
-    constexpr int NT = TN * WN;
+    constexpr int NT = TN * (4 / WM);
     const int TW = 1 << a.tw_log2, SR = 32 >> a.tw_log2, TH = NT * SR;
     const int LH = (TH - 1) * S + KH, LW = (TW - 1) * S + KH;
     ConvArgs b = a;
@@ -817,10 +623,7 @@ int launch_bx_cfg_s(const ConvArgs& a, int N, hipStream_t st) {
     b.single_buf = (KH == 3 && (a.Cin + 15) / 16 <= single_env) ? 1 : 0;
     size_t lds = (size_t)(b.single_buf ? 1 : 2) * (2 * NS) * LH * LW * 16;
     if (lds < 4 * 32 * 36 * sizeof(float)) lds = 4 * 32 * 36 * sizeof(float);   // the vector epilogue's four wave-private 32 x 36 patches
-    b.tiles_x = tdr_cdiv(a.OW, TW);
-    const int tiles_y = tdr_cdiv(a.OH, TH);
-    b.mtiles = tdr_cdiv(a.Cout, BM);
-    dim3 grid(b.tiles_x * tiles_y * b.mtiles, 1, N);
+    const dim3 grid = tile_grid(a, 32 * TM * WM, NT, N, b);
     // Multi-round launches (and the two-m-tile kernels, which spill with 9 slots): a 3-slot ring -- fragments requested three taps
     // ahead (an L2 round trip is longer than one tap of MFMAs) and the operand prefetch deferred to tap 6 (see the main loop).
     // Same-box step 59.1 -> 58.4 ms: 32 -> 32 @512^2 216 -> 196 us, 128 -> 128 @128^2 145 -> 129 us, 64 -> 64 @256^2 unchanged
@@ -828,41 +631,15 @@ int launch_bx_cfg_s(const ConvArgs& a, int N, hipStream_t st) {
     if constexpr (KH == 3 && S == 1 && SCH == SCH_HX2 && EPI == EPI_STD && !GATE) {
         static const int ring3 = tdr_tune_env("TDR_RING3") ? atoi(tdr_tune_env("TDR_RING3")) : 1;
         static const long ring_blocks3 = tdr_tune_env("TDR_RING_BLOCKS") ? atol(tdr_tune_env("TDR_RING_BLOCKS")) : 512;
-        if (ring3 && ((long)grid.x * N > ring_blocks3 || TM != 1)) {
-            auto kern = conv_bx3_kernel<KH, S, WM, TM, TN, EPI, GATE, SCH, 3>;
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_set = true;
-            }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, b);
-            TDR_LAUNCH_CHECK("conv_bx3_kernel(ring3)");
-            return TDR_OK;
-        }
+        if (ring3 && ((long)grid.x * N > ring_blocks3 || TM != 1))
+            return launch_conv<conv_bx3_kernel<KH, S, WM, TM, TN, EPI, GATE, SCH, 3>>("conv_bx3_kernel(ring3)", grid, lds, st, b);
     }
     if constexpr (KH == 3 && S == 1 && TM == 1 && SCH == SCH_HX2 && EPI == EPI_STD) {   // weight-fragment ring: single-round launches
         static const long ring_blocks = tdr_tune_env("TDR_RING_BLOCKS") ? atol(tdr_tune_env("TDR_RING_BLOCKS")) : 512;
-        if ((long)grid.x * N <= ring_blocks) {
-            auto kern = conv_bx3_kernel<KH, S, WM, TM, TN, EPI, GATE, SCH, 9>;
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_set = true;
-            }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, b);
-            TDR_LAUNCH_CHECK("conv_bx3_kernel(ring)");
-            return TDR_OK;
-        }
+        if ((long)grid.x * N <= ring_blocks)
+            return launch_conv<conv_bx3_kernel<KH, S, WM, TM, TN, EPI, GATE, SCH, 9>>("conv_bx3_kernel(ring)", grid, lds, st, b);
     }
-    auto kern = conv_bx3_kernel<KH, S, WM, TM, TN, EPI, GATE, SCH>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, b);
-    TDR_LAUNCH_CHECK("conv_bx3_kernel");
-    return TDR_OK;
+    return launch_conv<conv_bx3_kernel<KH, S, WM, TM, TN, EPI, GATE, SCH>>("conv_bx3_kernel", grid, lds, st, b);
 }
 
 template <int KH, int S, int WM, int TM, int TN, int EPI, bool GATE>
@@ -945,18 +722,18 @@ extern "C" int tdr_conv_force_cfg(int kh, int cfg) {
 }
 
 extern "C" int tdr_conv1x1_bx3_staged_set(int on) {
-    g_c1_bx3_staged = on ? 1 : 0;
+    g_c1_staged = on ? 1 : 0;
     return TDR_OK;
 }
 
 // tdr_conv_forward itself (its argument checks included), walked without a launch: the query pointer is per thread, so a convolution
 // issued from another thread meanwhile is launched as usual
 extern "C" int tdr_conv1x1_bx3_staged_takes(const TdrConvDesc* d) {
-    if (!d || d->wp_fmt != 1 || d->dil != 1 || d->KH != 1 || d->stride != 1) return 0;
+    if (!d || d->wp_fmt < 1 || d->wp_fmt > 3 || d->dil != 1 || d->KH != 1 || d->stride != 1) return 0;    // (fp32 rows: another file's kernels)
     int takes = 0;
-    g_c1_bx3_query = &takes;
+    g_c1_query = &takes;
     const int rc = tdr_conv_forward(d, nullptr);
-    g_c1_bx3_query = nullptr;
+    g_c1_query = nullptr;
     return rc == TDR_OK ? takes : 0;
 }
 

@@ -361,12 +361,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8) ? 1 : 2) void conv3x3_
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int j = lane & 31, kk = lane >> 5;
-    int logical;
-    {   // XCD-aware block order (as conv_bx3_kernel): the m-tiles of one pixel tile run back to back on one XCD
-        const int T = gridDim.x, b = blockIdx.x;
-        const int q = T >> 3, r = T & 7, xcd = b & 7, slot = b >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    const int logical = tdr_xcd_logical_block();    // the m-tiles of one pixel tile run back to back on one XCD
     const int mtile = logical % a.mtiles;
     int pt = logical / a.mtiles;
     const int tx = pt % a.tiles_x; pt /= a.tiles_x;

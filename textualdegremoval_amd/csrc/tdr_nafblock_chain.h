@@ -8,7 +8,7 @@
 //
 // Everything here is per pixel, so one workgroup owns 64 pixels x ALL channels and walks the chain without leaving
 // the CU: three back-to-back implicit GEMMs on the 2-way fp16 split (3 x v_mfma_f32_32x32x16_f16 per fp32 product,
-// fp32 accumulate -- same arithmetic and packed weights as conv1x1_hx2_kernel), LayerNorm as a cross-wave reduction
+// fp32 accumulate -- same arithmetic and packed weights as conv1x1_staged_kernel<..., SCH_HX2>), LayerNorm as a cross-wave reduction
 // through LDS, the SimpleGate product register-local (wave w owns channels [64w, 64w+64) and [256+64w, 256+64w+64) of
 // t4).  The four separate launches (conv3, norm2, conv4, conv5) move 201 MB per block at this level and are single-round,
 // latency-bound kernels (26.8 + 13.2 + 36.9 + 26.2 us); fused, the tile is read once (g, inp) and every tensor the

@@ -23,10 +23,12 @@ __device__ __forceinline__ void tdr_split3(float x, __bf16& h, __bf16& m, __bf16
 }
 
 typedef __bf16 tdr_bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 tdr_f16x8 __attribute__((ext_vector_type(8)));
 union TdrFrag {
     uint4 u;
     unsigned d[4];
     tdr_bf16x8 v;
+    tdr_f16x8 hv;
 };
 
 // element i of the fp32 row layout Wp[chunk][tap][ck][Mpad]
@@ -116,7 +118,6 @@ __device__ __forceinline__ void tdr_pack_bx3_alltaps9(const float* __restrict__ 
 }
 
 // the same fragment in the 2-way fp16 split layout Wp2[group][tap][mt][split(h, m)][lane][8 x f16]
-typedef _Float16 tdr_f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void tdr_pack_hx2_frag(const float* __restrict__ w, int Cin, int KH, int mode, int M, int Kch,
                                                   int KHe, int MT, long i, uint4* __restrict__ wp) {
     const int taps_e = KHe * KHe;

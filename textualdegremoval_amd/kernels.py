@@ -131,7 +131,7 @@ ATTN_F32 = False              # exact-fp32 attention products inside an fp16 ari
 ATTN_BX3 = True               # TDR_MATH=bx3: the frozen ViTs' attention on the 3-way bf16 split (False: exact fp32 MFMA, as in rounds 1 - 5)
 DWK_GENERIC = False           # the LDS-tiled generic depthwise kernels instead of the register-window ones (module switch: cross-check tests)
 SIDE_WGRAD = False            # (module switch: tests/test_hip_network.py::test_side_stream_weight_gradients_match)
-CONV1X1_STAGED = True         # TDR_MATH=bx3: eligible 1x1 launches on the float4-staged kernel (False: all on the generic kernel; conv_forward passes the
+CONV1X1_STAGED = True         # any arithmetic: eligible 1x1 launches on the float4-staged kernel (False: all on the generic kernel; conv_forward passes the
                               # switch on to the library -- tdr_conv1x1_bx3_staged_set -- whenever it changed; bit-identical either way)
 _conv1x1_staged_sent = True   # the library's own default
 _side_stream = None
@@ -529,7 +529,7 @@ def conv_forward(x, wp, Mpad, Cout, KH, stride=1, dil=1, pad=0, OH=None, OW=None
 
 
 def conv1x1_staged_takes(x, wp, Mpad, Cout, KH, *args, **kw):
-    """(arguments: exactly those of conv_forward)  True if conv_forward with the same arguments would run on the float4-staged 1x1 kernel of the bx3 arithmetic (under the current
+    """(arguments: exactly those of conv_forward)  True if conv_forward with the same arguments would run on the float4-staged 1x1 kernel, any arithmetic (under the current
     CONV1X1_STAGED and forced tile configuration); launches nothing.  Pass `out=` to ask about a particular output view."""
     lib = _lib.load()
     d, _ = _conv_desc(x, wp, Mpad, Cout, KH, *args, **kw)
