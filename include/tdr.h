@@ -23,8 +23,8 @@ extern "C" {
 /* C-ABI version: bumped with every incompatible change of this header (100 rounds 1-2, 101 round 3, 102 round 4, 103 - 104
  * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
  * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local; still 112,
- * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes -- no existing entry point or descriptor changed, and the binding resolves
- * every declared symbol when it loads the library, so a build without them is refused there); the
+ * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8 -- no existing entry point
+ * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there); the
  * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
 #define TDR_ABI_VERSION 112
 int tdr_version(void);
@@ -423,6 +423,18 @@ int tdr_ssim_y64(const float* img1, const float* img2, int H, int W, double* ws,
 int64_t tdr_niqe_ws_floats(int H, int W);
 int tdr_niqe_features(const float* y, int H, int W, int block, const double* window, const double* tables, int table_len,
                       float* ws, double* feats_out, void* stream);
+/* Byte images in, byte images out (csrc/tdr_imgio.hip; an addition to ABI 112): the host conversions around the network in the reference's evaluation
+ * loop, on the device.  img: uint8 [N][H][W][C] (HWC, as cv2 decodes), C in {1, 3, 6}; planes: float32 [N][C][Hp][Wp], Hp >= H, Wp >= W.
+ * swap_rb exchanges channels 0 and 2 of a 3-channel image (cv2.cvtColor BGR <-> RGB; other channel counts are left as they are, as in
+ * the reference).
+ *   tdr_img_u8_to_planes: imfrombytes(float32=True) + img2tensor(bgr2rgb) of utils/utils_image.py:102-126,194-218, plus the zero pad to
+ *     (Hp, Wp): planes[n][c][y][x] = float32(u) / 255.0f (the correctly rounded IEEE quotient numpy computes, from a 256-entry table),
+ *     0 for y >= H or x >= W.
+ *   tdr_planes_to_img_u8: tensor2img(rgb2bgr, np.uint8, (0, 1)) of :129-190 on the top-left (H, W) of the planes:
+ *     img = uint8(rint(min(max(v, 0), 1) * 255.0f)) -- float32 product, round half to even.  Finite inputs. */
+int tdr_img_u8_to_planes(const uint8_t* img, int N, int H, int W, int C, int swap_rb, float* out, int Hp, int Wp, void* stream);
+int tdr_planes_to_img_u8(const float* in, int N, int C, int Hp, int Wp, int swap_rb, uint8_t* img, int H, int W, void* stream);
+
 /* TLSC local average pooling -- `AvgPool2d.forward` of models/archs/nafnet_local_arch.py:10-75 (fast_imp = False, auto_pad):
  * out[p][y][x] = mean of the k1' x k2' box (k' = min(size, k)) whose top-left corner is (clamp(y - (H - hv) / 2, 0, hv - 1),
  * clamp(x - (W - wv) / 2, 0, wv - 1)), hv = H - k1' + 1, wv = W - k2' + 1: the valid box means replicate-padded back to H x W.

@@ -385,6 +385,8 @@ SIGNATURES = {
     'tdr_modgate_bwd': (i32, [c_fp, c_fp, f32, c_fp, c_fp, c_fp, i64, i32, i32, i32, c_fp, c_fp, c_fp, i64, c_fp]),
     'tdr_niqe_ws_floats': (i64, [i32, i32]),
     'tdr_niqe_features': (i32, [c_fp, i32, i32, i32, c_fp, c_fp, i32, c_fp, c_fp, c_fp]),
+    'tdr_img_u8_to_planes': (i32, [c_fp, i32, i32, i32, i32, i32, c_fp, i32, i32, c_fp]),
+    'tdr_planes_to_img_u8': (i32, [c_fp, i32, i32, i32, i32, i32, c_fp, i32, i32, c_fp]),
 }
 
 _lib = None

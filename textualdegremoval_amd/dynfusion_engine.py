@@ -90,6 +90,8 @@ def proj_table(P, blocks, device):
 def proj_fwd(P, blocks, kvf):
     """every projection of `blocks` in one launch -> (table, Kt [N, sum 10c])"""
     tab = proj_table(P, blocks, kvf.device)
+    if K._ws_capture_refs is not None:
+        K._ws_capture_refs.append(tab)       # a captured forward addresses the device table: it lives as long as the graph, whatever the cache does
     return tab, K.kvproj_fwd(tab.tab, tab.nseg, tab.ntiles, kvf, tab.ld)
 
 

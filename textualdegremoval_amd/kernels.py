@@ -342,9 +342,15 @@ class PackPlan:
     """Per-model cache of packed weights.  The first step records every (weight, mode) the engine asks for and
     packs it on the spot into a persistent buffer; from then on `run()` re-packs ALL of them with one
     multi-tensor launch at the start of a step (weights change once per step, in the optimiser) and
-    `pack_weights` returns the cached buffers without launching anything."""
+    `pack_weights` returns the cached buffers without launching anything.
+    `admit`: an optional set of `data_ptr()`s (inference.InferenceSession passes those of its network's parameters and buffers).  A weight
+    whose pointer is not in it is packed on the spot and NOT recorded: a forward also packs weights it derives per call (the folded
+    Wo.A of tdr_attn_fold_proj, the re-tiled transposed-convolution kernel of sfnet_engine.convt_fwd, per-image TLSC weights) -- an entry
+    keeps `w` alive and is keyed on its address, so recording those would grow the plan with every call and could hand a stale pack to a
+    later tensor at a recycled address."""
 
-    def __init__(self):
+    def __init__(self, admit=None):
+        self.admit = None if admit is None else frozenset(admit)
         self.entries = {}          # (ptr, shape, mode, math) -> (w, mode, math, PackedWeights)
         self.grouped = {}          # pack_weights_grouped: stacks of per-word matrices whose packs are views of one buffer
         self.table = None
@@ -356,6 +362,9 @@ class PackPlan:
         e = self.entries.get(key)
         if e is None:
             pw = _packed_buffer(w, mode, math)
+            if self.admit is not None and key[0] not in self.admit:
+                _pack_into(w, mode, pw)
+                return pw
             self.entries[key] = (w, mode, math, pw)
             self.dirty = True
             _pack_into(w, mode, pw)
@@ -433,6 +442,8 @@ def pack_weights_grouped(W, mode):
     G, Cout, Cin = W.shape
     assert W.is_contiguous()
     plan = _active_plan
+    if plan is not None and plan.admit is not None and W.data_ptr() not in plan.admit:
+        plan = None                        # (a restricted plan records the weights it admits only)
     key = ('grouped', W.data_ptr(), (G, Cout, Cin), mode, MATH, GRAD_SCALED)
     store = plan.grouped if plan is not None else None
     e = store.get(key) if store is not None else None
@@ -1274,6 +1285,32 @@ def pad_crop(x, Hd, Wd):
     assert x.is_contiguous()
     out = torch.empty(N, Cc, Hd, Wd, dtype=torch.float32, device=x.device)
     check(_lib.load().tdr_pad_crop(x.data_ptr(), N, Cc, Hs, Ws, out.data_ptr(), Hd, Wd, _stream()), 'tdr_pad_crop')
+    return out
+
+
+def img_u8_to_planes(img, Hp=None, Wp=None, swap_rb=True):
+    """img uint8 [N,H,W,C] (HWC bytes as cv2 decodes them, C in {1, 3, 6}) -> float32 [N,C,Hp,Wp]: float32(u) / 255 as numpy divides,
+    channels 0 and 2 of a 3-channel image exchanged when swap_rb, zero-padded to (Hp, Wp) (default: no pad) -- imfrombytes(float32=True) +
+    img2tensor(bgr2rgb) of the reference's utils/utils_image.py and the network's own pad, one launch (csrc/tdr_imgio.hip)"""
+    assert img.dtype == torch.uint8 and img.dim() == 4 and img.is_contiguous()
+    N, H, W, Cc = img.shape
+    Hp, Wp = H if Hp is None else int(Hp), W if Wp is None else int(Wp)
+    out = torch.empty(N, Cc, Hp, Wp, dtype=torch.float32, device=img.device)
+    check(_lib.load().tdr_img_u8_to_planes(img.data_ptr(), N, H, W, Cc, int(bool(swap_rb)), out.data_ptr(), Hp, Wp, _stream()),
+          'tdr_img_u8_to_planes')
+    return out
+
+
+def planes_to_img_u8(x, H=None, W=None, swap_rb=True):
+    """x float32 [N,C,Hp,Wp] -> uint8 [N,H,W,C]: the top-left (H, W) of every plane (default: all of it), clamped to [0, 1], times 255,
+    rounded half to even, channels 0 and 2 of a 3-channel image exchanged when swap_rb -- tensor2img(rgb2bgr, np.uint8, (0, 1)) of the
+    reference's utils/utils_image.py, one launch, the bytes stay on the device"""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    N, Cc, Hp, Wp = x.shape
+    H, W = Hp if H is None else int(H), Wp if W is None else int(W)
+    out = torch.empty(N, H, W, Cc, dtype=torch.uint8, device=x.device)
+    check(_lib.load().tdr_planes_to_img_u8(x.data_ptr(), N, Cc, Hp, Wp, int(bool(swap_rb)), out.data_ptr(), H, W, _stream()),
+          'tdr_planes_to_img_u8')
     return out
 
 

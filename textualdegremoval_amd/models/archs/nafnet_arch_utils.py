@@ -32,6 +32,24 @@ def infer_fwd(what, fwd, names, params, cfg, *images):
         K.set_pack_plan(prev)
 
 
+def infer_spec(net):
+    """(fwd, names, params, cfg) of a network class routed through infer_fwd: the engine's whole-network forward in the shape
+    `fwd(P, cfg, *images, keep=)` with the positional images of `net.forward`, the parameter names / tensors it reads (registration order,
+    unused ones left out where the class does so) and the class's cfg.  Every such class answers with its `infer_spec()` method -- its own
+    `forward` hands exactly this to infer_fwd, and inference.InferenceSession runs it under a pack plan of its own."""
+    spec = getattr(net, 'infer_spec', None)
+    if spec is None:
+        raise TypeError(f'{type(net).__name__} has no infer_spec(): not a network routed through nafnet_arch_utils.infer_fwd')
+    return spec()
+
+
+def unguided(fwd):
+    """the one-image form of a guided whole-network forward (Restormer / PromptIR / DRSformer without a reference: ref=None)"""
+    def run(P, cfg, x, keep=True):
+        return fwd(P, cfg, x, None, keep=keep)
+    return run
+
+
 class LayerNormFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):

@@ -179,7 +179,12 @@ class DRSformer200L_SPA_RefFusion(nn.Module):
         _, _, h, w = x.shape
         return K.pad_crop(x.contiguous(), -(-h // mult) * mult, -(-w // mult) * mult)
 
-    def forward(self, inp_img, ref_img):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = zip(*self.used_named_parameters())
-        out = infer_fwd('DRSformer200L_SPA_RefFusion', DE.net_fwd, names, params, self.cfg, inp_img, ref_img)
+        return DE.net_fwd, names, params, self.cfg
+
+    def forward(self, inp_img, ref_img):
+        fwd, names, params, cfg = self.infer_spec()
+        out = infer_fwd('DRSformer200L_SPA_RefFusion', fwd, names, params, cfg, inp_img, ref_img)
         return out if out is not None else _NetFn.apply(inp_img, ref_img, list(names), self.cfg, *params)

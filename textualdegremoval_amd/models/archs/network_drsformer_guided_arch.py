@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from ... import drsformer_engine as DE
 from ... import kernels as K
-from .nafnet_arch_utils import infer_fwd, require_gpu
+from .nafnet_arch_utils import infer_fwd, require_gpu, unguided
 from .network_drsformer_guided_200L_SPA_arch import TransformerBlock, TransformerResFusionBlock
 from .network_restormer_guided_arch import Downsample, Encoder, OverlapPatchEmbed, Upsample, _named  # noqa: F401
 
@@ -174,9 +174,14 @@ class DRSformer(nn.Module):
         self.cfg = dict(inp_channels=inp_channels, out_channels=out_channels, dim=dim, num_blocks=list(num_blocks), heads=list(heads),
                         ffn_expansion_factor=ffn_expansion_factor, bias=bias, LayerNorm_type=LayerNorm_type, mefc=True)
 
-    def forward(self, inp_img):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = _named(self)
-        out = infer_fwd('DRSformer', DE.net_fwd, names, params, self.cfg, inp_img, None)
+        return unguided(DE.net_fwd), names, params, self.cfg
+
+    def forward(self, inp_img):
+        fwd, names, params, cfg = self.infer_spec()
+        out = infer_fwd('DRSformer', fwd, names, params, cfg, inp_img)
         return out if out is not None else _NetFn.apply(inp_img, None, names, self.cfg, *params)
 
 
@@ -238,7 +243,12 @@ class DRSformerRefFusion(nn.Module):
         _, _, h, w = x.shape
         return K.pad_crop(x.contiguous(), -(-h // mult) * mult, -(-w // mult) * mult)
 
-    def forward(self, inp_img, ref_img):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = _named(self)
-        out = infer_fwd('DRSformerRefFusion', DE.net_fwd, names, params, self.cfg, inp_img, ref_img)
+        return DE.net_fwd, names, params, self.cfg
+
+    def forward(self, inp_img, ref_img):
+        fwd, names, params, cfg = self.infer_spec()
+        out = infer_fwd('DRSformerRefFusion', fwd, names, params, cfg, inp_img, ref_img)
         return out if out is not None else _NetFn.apply(inp_img, ref_img, names, self.cfg, *params)

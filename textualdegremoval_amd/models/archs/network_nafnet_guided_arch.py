@@ -218,9 +218,14 @@ class NAFNet(_NAFBase):
         m = self.padder_size
         return K.pad_crop(x.contiguous(), -(-h // m) * m, -(-w // m) * m)
 
-    def forward(self, inp):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = _named(self)
-        out = _infer_fwd('NAFNet', E.unet_fwd, names, params, self.cfg, inp)
+        return E.unet_fwd, names, params, self.cfg
+
+    def forward(self, inp):
+        fwd, names, params, cfg = self.infer_spec()
+        out = _infer_fwd('NAFNet', fwd, names, params, cfg, inp)
         return out if out is not None else _UNetFn.apply(inp, names, self.cfg, *params)
 
 
@@ -254,9 +259,14 @@ class NAFNetRefFusion(_NAFBase):
         from ... import kernels as K
         return K.pad_crop(x.contiguous(), -(-h // mult) * mult, -(-w // mult) * mult)
 
-    def forward(self, inp, ref):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = _named(self)
-        out = _infer_fwd('NAFNetRefFusion', E.net_fwd, names, params, self.cfg, inp, ref)
+        return E.net_fwd, names, params, self.cfg
+
+    def forward(self, inp, ref):
+        fwd, names, params, cfg = self.infer_spec()
+        out = _infer_fwd('NAFNetRefFusion', fwd, names, params, cfg, inp, ref)
         return out if out is not None else _NetFn.apply(inp, ref, names, self.cfg, *params)
 
 
@@ -277,17 +287,15 @@ class NAFNetLocal(NAFNet):
         self.ksizes = E.tlsc_kernel_sizes(self.cfg, self.train_size)
         self.eval()
 
-    def forward(self, inp):
-        from ... import kernels as K
-        require_gpu(inp, 'NAFNetLocal')
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = _named(self)
-        # a pass that keeps nothing, its weights packed outside any PackPlan (as nafnet_arch_utils.infer_fwd runs one)
-        prev = K.set_pack_plan(None)
-        try:
-            with torch.no_grad():
-                return E.unet_fwd(dict(zip(names, [p.detach() for p in params])), self.cfg, inp.detach(), local=self.ksizes, keep=False)[0]
-        finally:
-            K.set_pack_plan(prev)
+        return functools.partial(E.unet_fwd, local=self.ksizes), names, params, self.cfg
+
+    def forward(self, inp):
+        fwd, names, params, cfg = self.infer_spec()
+        with torch.no_grad():                # inference only: a pass that keeps nothing, whatever the caller's grad mode
+            return _infer_fwd('NAFNetLocal', fwd, names, params, cfg, inp)
 
 
 class NAFNetLocal_RefFusion(NAFNetRefFusion):

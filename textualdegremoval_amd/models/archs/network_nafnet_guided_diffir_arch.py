@@ -149,10 +149,15 @@ class NAFNetDynamicFusion(nn.Module):
         m = self.padder_size
         return K.pad_crop(x.contiguous(), -(-h // m) * m, -(-w // m) * m)
 
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
+        names, params = _named(self)
+        return D.dyn_unet_fwd, names, params, self.cfg
+
     def forward(self, inp, k_v):
         D.flat_kv(k_v, inp.shape[0])          # (shape checks first: a 20-word embedding fails as in the reference, defect R10)
-        names, params = _named(self)
-        out = _infer_fwd('NAFNetDynamicFusion', D.dyn_unet_fwd, names, params, self.cfg, inp, k_v)
+        fwd, names, params, cfg = self.infer_spec()
+        out = _infer_fwd('NAFNetDynamicFusion', fwd, names, params, cfg, inp, k_v)
         return out if out is not None else _DynNetFn.apply(inp, k_v, names, self.cfg, *params)
 
 

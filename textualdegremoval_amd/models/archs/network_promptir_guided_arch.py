@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from ... import kernels as K
 from ... import promptir_engine as PE
-from .nafnet_arch_utils import infer_fwd, require_gpu
+from .nafnet_arch_utils import infer_fwd, require_gpu, unguided
 from .network_restormer_guided_arch import (Attention, BiasFree_LayerNorm, Downsample, Encoder, FeedForward,  # noqa: F401
                                             LayerNorm, OverlapPatchEmbed, ResidualBlock, TransformerBlock,
                                             TransformerResFusionBlock, Upsample, WithBias_LayerNorm, _named, make_layer)
@@ -140,9 +140,14 @@ class PromptIR(nn.Module):
     def used_named_parameters(self):
         return [(k, p) for k, p in self.named_parameters() if not k.startswith(self.unused_parameter_prefixes)]
 
-    def forward(self, inp_img, noise_emb=None):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = zip(*self.used_named_parameters())
-        out = infer_fwd('PromptIR', PE.net_fwd, names, params, self.cfg, inp_img, None)
+        return unguided(PE.net_fwd), names, params, self.cfg
+
+    def forward(self, inp_img, noise_emb=None):
+        fwd, names, params, cfg = self.infer_spec()
+        out = infer_fwd('PromptIR', fwd, names, params, cfg, inp_img)
         return out if out is not None else _NetFn.apply(inp_img, None, list(names), self.cfg, *params)
 
 
@@ -238,7 +243,12 @@ class PromptIRRefFusion(nn.Module):
         _, _, h, w = x.shape
         return K.pad_crop(x.contiguous(), -(-h // mult) * mult, -(-w // mult) * mult)
 
-    def forward(self, inp_img, ref_img, noise_emb=None):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = zip(*self.used_named_parameters())
-        out = infer_fwd('PromptIRRefFusion', PE.net_fwd, names, params, self.cfg, inp_img, ref_img)
+        return PE.net_fwd, names, params, self.cfg
+
+    def forward(self, inp_img, ref_img, noise_emb=None):
+        fwd, names, params, cfg = self.infer_spec()
+        out = infer_fwd('PromptIRRefFusion', fwd, names, params, cfg, inp_img, ref_img)
         return out if out is not None else _NetFn.apply(inp_img, ref_img, list(names), self.cfg, *params)

@@ -15,7 +15,7 @@ import torch.nn as nn
 from ... import engine as E
 from ... import kernels as K
 from ... import restormer_engine as R
-from .nafnet_arch_utils import infer_fwd, require_gpu
+from .nafnet_arch_utils import infer_fwd, require_gpu, unguided
 
 
 def _named(module):
@@ -279,9 +279,14 @@ class Restormer(nn.Module):
                         num_refinement_blocks=num_refinement_blocks, heads=list(heads), ffn_expansion_factor=ffn_expansion_factor,
                         bias=bias, LayerNorm_type=LayerNorm_type, dual_pixel_task=dual_pixel_task)
 
-    def forward(self, inp_img):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = _named(self)
-        out = infer_fwd('Restormer', R.net_fwd, names, params, self.cfg, inp_img, None)
+        return unguided(R.net_fwd), names, params, self.cfg
+
+    def forward(self, inp_img):
+        fwd, names, params, cfg = self.infer_spec()
+        out = infer_fwd('Restormer', fwd, names, params, cfg, inp_img)
         return out if out is not None else _UNetFn.apply(inp_img, names, self.cfg, *params)
 
 
@@ -348,7 +353,12 @@ class RestormerRefFusion(nn.Module):
         _, _, h, w = x.shape
         return K.pad_crop(x.contiguous(), -(-h // mult) * mult, -(-w // mult) * mult)
 
-    def forward(self, inp_img, ref_img):
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the no-gradient route: nafnet_arch_utils.infer_spec"""
         names, params = _named(self)
-        out = infer_fwd('RestormerRefFusion', R.net_fwd, names, params, self.cfg, inp_img, ref_img)
+        return R.net_fwd, names, params, self.cfg
+
+    def forward(self, inp_img, ref_img):
+        fwd, names, params, cfg = self.infer_spec()
+        out = infer_fwd('RestormerRefFusion', fwd, names, params, cfg, inp_img, ref_img)
         return out if out is not None else _NetFn.apply(inp_img, ref_img, names, self.cfg, *params)

@@ -422,12 +422,29 @@ class RefGuidedImageCleanModel(BaseModel):
         _, _, h, w = self.output.size()
         self.output = self.output[:, :, 0:h - mod_pad_h * scale, 0:w - mod_pad_w * scale]
 
+    def _val_session(self, net):
+        """`val: {session: true}`: one inference.InferenceSession per validated network -- weights packed once per validation, the
+        forward of each image shape replayed as a hipGraph from a pool of its own (not the train step's).  A call outside
+        nondist_validation re-packs first: the optimiser may have stepped since the last one."""
+        from ..inference import InferenceSession
+        bare = self.get_bare_model(net)
+        sessions = self.__dict__.setdefault('_val_sessions', {})
+        sess = sessions.get(id(bare))
+        if sess is None:
+            sess = sessions[id(bare)] = InferenceSession(bare)
+        elif not getattr(self, '_val_refreshed', False):
+            sess.refresh()
+        return sess
+
     def nonpad_test(self, img=None):
         img = self.lq if img is None else img
         net = self.net_g_ema if hasattr(self, 'net_g_ema') else self.net_g
         net.eval()
-        with torch.no_grad():
-            pred = net(img, self.ref)
+        if (self.opt.get('val') or {}).get('session', False):
+            pred = self._val_session(net)(img, self.ref)
+        else:
+            with torch.no_grad():
+                pred = net(img, self.ref)
         self.output = pred[-1] if isinstance(pred, list) else pred
         if net is self.net_g:
             self.net_g.train()
@@ -443,6 +460,15 @@ class RefGuidedImageCleanModel(BaseModel):
             self.metric_results = {m: 0 for m in self.opt['val']['metrics'].keys()}
         window_size = self.opt['val'].get('window_size', 0)
         test = partial(self.pad_test, window_size) if window_size else self.nonpad_test
+        for sess in getattr(self, '_val_sessions', {}).values():       # (val.session) the weights moved since the last validation
+            sess.refresh()
+        self._val_refreshed = True
+        try:
+            return self._validate(dataloader, test, with_metrics, rgb2bgr, use_image)
+        finally:
+            self._val_refreshed = False
+
+    def _validate(self, dataloader, test, with_metrics, rgb2bgr, use_image):
         cnt = 0
         for val_data in dataloader:
             self.feed_data(val_data)
