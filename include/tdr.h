@@ -23,7 +23,8 @@ extern "C" {
 /* C-ABI version: bumped with every incompatible change of this header (100 rounds 1-2, 101 round 3, 102 round 4, 103 - 104
  * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
  * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local; still 112,
- * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8 -- no existing entry point
+ * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8, then
+ * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL -- no existing entry point
  * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there); the
  * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
 #define TDR_ABI_VERSION 112
@@ -930,6 +931,16 @@ int tdr_region_affine_fwd(const float* x, int64_t x_ns, const float* ph, const f
 int tdr_region_affine_bwd(const float* dy, int64_t dy_ns, const float* x, int64_t x_ns, const float* ph, const float* pl, float shift,
                           const float* mean, int q, int N, int C, int H, int W, float* dx, int64_t dx_ns, float* dph, float* dpl, float* ws,
                           void* stream);
+/* Forward only: [GELU ->] Gap + Patch_ap of one ResBlock in two launches, no activation tensor in between.  z dense [N][C][H][W] (C, H, W
+ * even), v = gelu(z) (act = 1) or z (act = 0); channels c < C/2 are the Gap half (m = mean of v over the plane, a = gap_h[c] + 1,
+ * b = gap_d[c]), channels c >= C/2 the Patch_ap half (m = mean of v over the pixel's quadrant g, a = pa_h[4 (c - C/2) + g], b = pa_l[..]):
+ *   r = v * a + m * (b - a)          -- the arithmetic of tdr_region_affine_fwd.
+ * sums:  part [N * C][4][chunks], one float per (plane, quadrant, chunk of at most rows_per_chunk quadrant rows), fixed-order sums;
+ *        chunks = ceil(H / 2 / rows_per_chunk) <= 65535.   apply: adds the partials in index order (Gap: (s0 + s1) + (s2 + s3)) and writes r; r may be z.
+ * Both use float4 accesses when W / 2 is a multiple of 4 and the bases are 16-byte aligned, scalar ones otherwise. */
+int tdr_sf_act_region_sums(const float* z, int N, int C, int H, int W, int rows_per_chunk, int chunks, int act, float* part, void* stream);
+int tdr_sf_act_region_apply(const float* z, const float* gap_h, const float* gap_d, const float* pa_h, const float* pa_l, const float* part,
+                            int N, int C, int H, int W, int rows_per_chunk, int chunks, int act, float* r, void* stream);
 /* (the pooled vectors come from tdr_plane_mean above) */
 /* dynamic_filter (:152-192) + SFconv (:195-236) on the pooled vectors ap [N][c], one workgroup:
  *   taps [N][G * KK] = softmax over the KK = k * k taps of each (image, group) of BatchNorm2d_train(conv1x1(ap)) -- the running buffers and
@@ -952,7 +963,8 @@ typedef struct TdrSfDynVecBwdDesc {
 } TdrSfDynVecBwdDesc;
 int tdr_sf_dyn_vec_bwd(const TdrSfDynVecBwdDesc* d, void* stream);
 /* low = k x k stencil of the reflection-padded planes with taps[n][c / (C / groups)]; mix = x * ah[n][c] + low * (al - ah)[n][c]
- * (= high * ah + low * al with high = x - low): the operand of SFconv's `out` convolution */
+ * (= high * ah + low * al with high = x - low): the operand of SFconv's `out` convolution.  low may be NULL (a forward pass that keeps
+ * nothing): mix is the same bit for bit. */
 int tdr_sf_dynfilt_fwd(const float* x, int64_t x_ns, const float* taps, const float* ah, const float* al, int N, int C, int groups, int H,
                        int W, int k, float* low, float* mix, void* stream);
 /* backward, reductions: dah[n][c] = sum dmix * (x - low), dal = sum dmix * low, dtaps[n][g][t] = sum_{c in g} (al - ah) sum_px dmix * xpad(t) */

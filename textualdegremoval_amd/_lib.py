@@ -246,6 +246,8 @@ SIGNATURES = {
     'tdr_instnorm_bwd': (i32, [c_fp] * 5 + [i32, i32, i32] + [c_fp] * 5),
     'tdr_region_affine_fwd': (i32, [c_fp, i64, c_fp, c_fp, f32, i32, i32, i32, i32, i32, c_fp, i64, c_fp, c_fp]),
     'tdr_region_affine_bwd': (i32, [c_fp, i64, c_fp, i64, c_fp, c_fp, f32, c_fp, i32, i32, i32, i32, i32, c_fp, i64, c_fp, c_fp, c_fp, c_fp]),
+    'tdr_sf_act_region_sums': (i32, [c_fp, i32, i32, i32, i32, i32, i32, i32, c_fp, c_fp]),
+    'tdr_sf_act_region_apply': (i32, [c_fp] * 6 + [i32] * 7 + [c_fp, c_fp]),
     'tdr_sf_dyn_vec_fwd': (i32, [C.POINTER(TdrSfDynVecDesc), c_fp]),
     'tdr_sf_dyn_vec_bwd': (i32, [C.POINTER(TdrSfDynVecBwdDesc), c_fp]),
     'tdr_sf_dynfilt_fwd': (i32, [c_fp, i64, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, c_fp, c_fp, c_fp]),

@@ -5,6 +5,7 @@
 //   InstanceNorm2d(affine) (SCM, :208)                                            tdr_instnorm_fwd / _bwd
 //   Gap (:101-117) and Patch_ap (:239-265): out = x * A[c, region] + mean_region(x) * B[c, region] over the whole plane (Gap) or its four
 //   quadrants (Patch_ap), channel slices in place                                 tdr_region_affine_fwd / _bwd
+//   forward only: [GELU ->] Gap + Patch_ap of a ResBlock on quadrant tiles, two launches   tdr_sf_act_region_sums / _apply
 //   dynamic_filter (:152-192) + SFconv (:195-236):
 //       per-plane mean                                                             (tdr_plane_mean, csrc/tdr_prompt.hip)
 //       the vector pipeline on [N, c] pooled vectors -- 1x1 conv -> BatchNorm over the batch (running buffers moved) -> softmax over the
@@ -38,9 +39,9 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// y = gelu(z), z = x + bias[channel] (bias optional; z written back when z_out is given -- in place over x is fine)
-__global__ void gelu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ bias, int C, int HW, float* __restrict__ z_out,
-                                float* __restrict__ y, long n) {
+// y = gelu(z), z = x + bias[channel] (bias optional; z written back when z_out is given -- in place over x is fine, and so is y over x:
+// the forward-only walk activates in place; hence no __restrict__ on the three)
+__global__ void gelu_fwd_kernel(const float* x, const float* __restrict__ bias, int C, int HW, float* z_out, float* y, long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float z = x[i];
@@ -167,9 +168,88 @@ __global__ __launch_bounds__(256) void region_affine_bwd_kernel(const float* __r
     }
 }
 
+// ---- forward only: [GELU ->] Gap on channels [0, C/2) + Patch_ap on channels [C/2, C) of a dense [N][C][H][W], no activation tensor in
+// between.  Two passes over the quadrant tiles; the grid (N * C planes, 4 quadrants, chunks) grows with the pixel count, so one image at
+// the first level fills the part where region_affine_fwd_kernel launches 16 + 64 workgroups.
+// pass 1: part[plane][quadrant][chunk] = sum of v = act ? gelu(z) : z over at most rpc rows of the quadrant (fixed order, no atomics)
+template <bool VEC>
+__global__ __launch_bounds__(256) void act_region_sums_kernel(const float* __restrict__ z, int H, int W, int rpc, int act,
+                                                             float* __restrict__ part) {
+    __shared__ float red[4];
+    const int chunk = blockIdx.z, g = blockIdx.y, chunks = gridDim.z;
+    const long p = blockIdx.x;
+    const int qh = H / 2, qw = W / 2, r0 = chunk * rpc, rows = min(rpc, qh - r0);
+    const float* zp = z + p * H * W + (long)((g >> 1) * qh + r0) * W + (g & 1) * qw;
+    float s = 0.f;
+    if (VEC) {
+        const int q4 = qw >> 2;
+        for (int i = threadIdx.x; i < rows * q4; i += 256) {
+            const float4 v = *reinterpret_cast<const float4*>(zp + (long)(i / q4) * W + 4 * (i % q4));
+            s += act ? (gelu_f(v.x) + gelu_f(v.y)) + (gelu_f(v.z) + gelu_f(v.w)) : (v.x + v.y) + (v.z + v.w);
+        }
+    } else {
+        for (int i = threadIdx.x; i < rows * qw; i += 256) {
+            const float v = zp[(long)(i / qw) * W + i % qw];
+            s += act ? gelu_f(v) : v;
+        }
+    }
+    const float t = block_sum256(s, red);
+    if (threadIdx.x == 0) part[(p * 4 + g) * chunks + chunk] = t;
+}
+// pass 2: m = the quadrant's mean (Patch_ap; partials added in index order) or the plane's (Gap: (s0 + s1) + (s2 + s3)),
+// r = v * a + m * (b - a) with v recomputed from z.  r may be z itself (every element is read and written by one thread).
+template <bool VEC>
+__global__ __launch_bounds__(256) void act_region_apply_kernel(const float* z, const float* __restrict__ gap_h, const float* __restrict__ gap_d,
+                                                              const float* __restrict__ pa_h, const float* __restrict__ pa_l,
+                                                              const float* __restrict__ part, int C, int H, int W, int rpc, int act, float* r) {
+    const int chunk = blockIdx.z, g = blockIdx.y, chunks = gridDim.z;
+    const long p = blockIdx.x;
+    const int c = (int)(p % C), h = C / 2;
+    const int qh = H / 2, qw = W / 2, r0 = chunk * rpc, rows = min(rpc, qh - r0);
+    const float* pp = part + p * 4 * chunks;
+    float m, a, b;
+    if (c < h) {
+        float s[4];
+        for (int q = 0; q < 4; ++q) {
+            s[q] = 0.f;
+            for (int j = 0; j < chunks; ++j) s[q] += pp[q * chunks + j];
+        }
+        m = ((s[0] + s[1]) + (s[2] + s[3])) / (H * W);
+        a = gap_h[c] + 1.f;
+        b = gap_d[c];
+    } else {
+        float s = 0.f;
+        for (int j = 0; j < chunks; ++j) s += pp[g * chunks + j];
+        m = s / (qh * qw);
+        const int k = 4 * (c - h) + g;
+        a = pa_h[k];
+        b = pa_l[k];
+    }
+    const float mb = m * (b - a);
+    const long off = p * H * W + (long)((g >> 1) * qh + r0) * W + (g & 1) * qw;
+    const float* zp = z + off;
+    float* rp = r + off;
+    if (VEC) {
+        const int q4 = qw >> 2;
+        for (int i = threadIdx.x; i < rows * q4; i += 256) {
+            const long o = (long)(i / q4) * W + 4 * (i % q4);
+            float4 v = *reinterpret_cast<const float4*>(zp + o);
+            if (act) { v.x = gelu_f(v.x); v.y = gelu_f(v.y); v.z = gelu_f(v.z); v.w = gelu_f(v.w); }
+            v.x = v.x * a + mb; v.y = v.y * a + mb; v.z = v.z * a + mb; v.w = v.w * a + mb;
+            *reinterpret_cast<float4*>(rp + o) = v;
+        }
+    } else {
+        for (int i = threadIdx.x; i < rows * qw; i += 256) {
+            const long o = (long)(i / qw) * W + i % qw;
+            const float v = act ? gelu_f(zp[o]) : zp[o];
+            rp[o] = v * a + mb;
+        }
+    }
+}
+
 __device__ __forceinline__ int reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
 
-// low = stencil(x; taps[n][g]) with reflection padding; mix = x * ah + low * (al - ah)
+// low = stencil(x; taps[n][g]) with reflection padding; mix = x * ah + low * (al - ah); low may be null (forward-only walk: not kept)
 __global__ __launch_bounds__(256) void dynfilt_fwd_kernel(const float* __restrict__ x, long x_ns, const float* __restrict__ taps, const float* __restrict__ ah,
                                                          const float* __restrict__ al, int C, int cg, int H, int W, int k,
                                                          float* __restrict__ low, float* __restrict__ mix) {
@@ -184,7 +264,7 @@ __global__ __launch_bounds__(256) void dynfilt_fwd_kernel(const float* __restric
     float a = 0.f;
     for (int t = 0; t < k * k; ++t) a += tp[t] * xp[(long)reflect(yy + t / k - p, H) * W + reflect(xx + t % k - p, W)];
     const long o = ((long)n * C + c) * H * W + i;
-    low[o] = a;
+    if (low) low[o] = a;
     const float h = ah[(long)n * C + c], l = al[(long)n * C + c];
     mix[o] = xp[i] * h + a * (l - h);
 }
@@ -572,6 +652,43 @@ extern "C" int tdr_region_affine_bwd(const float* dy, int64_t dy_ns, const float
     TDR_LAUNCH_CHECK("region_affine_bwd_kernel");
     return TDR_OK;
 }
+namespace {
+bool act_region_shape_ok(int N, int C, int H, int W, int rpc, int chunks) {
+    return N > 0 && C > 0 && C % 2 == 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && (long)H * W < (1L << 31) && (long)N * C < (1L << 31) &&
+           rpc >= 1 && chunks >= 1 && chunks <= 65535 && (long)(chunks - 1) * rpc < H / 2 && (long)chunks * rpc >= H / 2;
+}
+// float4 rows: the quadrant width a multiple of 4 (then every row of every quadrant starts at a multiple of 4 floats) and an aligned base
+bool act_region_vec(const void* a, const void* b, int W) {
+    return (W / 2) % 4 == 0 && reinterpret_cast<uintptr_t>(a) % 16 == 0 && reinterpret_cast<uintptr_t>(b) % 16 == 0;
+}
+}  // namespace
+extern "C" int tdr_sf_act_region_sums(const float* z, int N, int C, int H, int W, int rows_per_chunk, int chunks, int act, float* part,
+                                      void* stream) {
+    TDR_REQUIRE(z && part && (act == 0 || act == 1), "tdr_sf_act_region_sums: bad argument");
+    TDR_REQUIRE(act_region_shape_ok(N, C, H, W, rows_per_chunk, chunks), "tdr_sf_act_region_sums: bad shape");
+    const dim3 grid(N * C, 4, chunks);          // planes in x: no 65535 limit on N * C
+    if (act_region_vec(z, z, W))
+        hipLaunchKernelGGL(act_region_sums_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, z, H, W, rows_per_chunk, act, part);
+    else
+        hipLaunchKernelGGL(act_region_sums_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, z, H, W, rows_per_chunk, act, part);
+    TDR_LAUNCH_CHECK("act_region_sums_kernel");
+    return TDR_OK;
+}
+extern "C" int tdr_sf_act_region_apply(const float* z, const float* gap_h, const float* gap_d, const float* pa_h, const float* pa_l,
+                                       const float* part, int N, int C, int H, int W, int rows_per_chunk, int chunks, int act, float* r,
+                                       void* stream) {
+    TDR_REQUIRE(z && gap_h && gap_d && pa_h && pa_l && part && r && (act == 0 || act == 1), "tdr_sf_act_region_apply: bad argument");
+    TDR_REQUIRE(act_region_shape_ok(N, C, H, W, rows_per_chunk, chunks), "tdr_sf_act_region_apply: bad shape");
+    const dim3 grid(N * C, 4, chunks);          // planes in x: no 65535 limit on N * C
+    if (act_region_vec(z, r, W))
+        hipLaunchKernelGGL(act_region_apply_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, z, gap_h, gap_d, pa_h, pa_l, part, C, H, W,
+                           rows_per_chunk, act, r);
+    else
+        hipLaunchKernelGGL(act_region_apply_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, z, gap_h, gap_d, pa_h, pa_l, part, C, H, W,
+                           rows_per_chunk, act, r);
+    TDR_LAUNCH_CHECK("act_region_apply_kernel");
+    return TDR_OK;
+}
 extern "C" int tdr_sf_dyn_vec_fwd(const TdrSfDynVecDesc* d, void* stream) {
     TDR_REQUIRE(d && d->ap && d->wconv && d->bn_w && d->bn_b && d->run_mean && d->run_var && d->fc_w && d->fc_b && d->f0_w && d->f0_b &&
                     d->f1_w && d->f1_b && d->taps && d->ah && d->al && d->xhat && d->rstd && d->z && d->att,
@@ -605,7 +722,7 @@ extern "C" int tdr_sf_dyn_vec_bwd(const TdrSfDynVecBwdDesc* d, void* stream) {
 }
 extern "C" int tdr_sf_dynfilt_fwd(const float* x, int64_t x_ns, const float* taps, const float* ah, const float* al, int N, int C, int groups,
                                   int H, int W, int k, float* low, float* mix, void* stream) {
-    TDR_REQUIRE(x && taps && ah && al && low && mix && (k == 3 || k == 5) && C % groups == 0 && H > k / 2 && W > k / 2,
+    TDR_REQUIRE(x && taps && ah && al && mix && (k == 3 || k == 5) && C % groups == 0 && H > k / 2 && W > k / 2,
                 "tdr_sf_dynfilt_fwd: bad argument");
     hipLaunchKernelGGL(dynfilt_fwd_kernel, dim3(tdr_cdiv((long)H * W, 256), C, N), dim3(256), 0, (hipStream_t)stream, x, (long)x_ns, taps, ah, al,
                        C, C / groups, H, W, k, low, mix);

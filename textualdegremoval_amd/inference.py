@@ -62,13 +62,52 @@ def pointer_tuple(net):
     return tuple(t.data_ptr() for t in list(net.parameters()) + list(net.buffers()))
 
 
+def tensor_slots(net):
+    """where the parameters and buffers of `net` live: (owner's dict, key) per tensor, each tensor once, in pointer_tuple's order --
+    parameters, then buffers.  Walking the module tree costs about a microsecond per module (1.2 ms for SFNet at num_res 16, on every
+    call); looking the slots up again costs a dict access each and still sees what pointer_tuple sees: a tensor moved by `.to()`
+    (same slot, other data_ptr) and a re-assigned one (same slot, other tensor)."""
+    slots = []
+    for attr in ('_parameters', '_buffers'):
+        seen = set()
+        for m in net.modules():
+            d = getattr(m, attr)
+            for k, t in d.items():
+                if t is not None and id(t) not in seen:
+                    seen.add(id(t))
+                    slots.append((d, k))
+    return slots
+
+
+def slot_pointers(slots):
+    """the data_ptr() of every slot, None once a slot is empty or gone (then nothing compares equal to it)"""
+    try:
+        return tuple(d[k].data_ptr() for d, k in slots)
+    except (KeyError, AttributeError):
+        return None
+
+
+def clone_out(out):
+    """a fresh copy of a captured entry's static output: one tensor, or a list of them (SFNet answers [out 1/4, out 1/2, out full]) ->
+    a tensor / a list of fresh tensors"""
+    if isinstance(out, (list, tuple)):
+        return [t.clone() for t in out]
+    return out.clone()
+
+
+def full_size(out):
+    """the output an image is written from: the tensor itself, or the last of a multi-scale list (the reference's validation reads preds[-1])"""
+    return out[-1] if isinstance(out, (list, tuple)) else out
+
+
 class InferenceSession:
     """`net`: any arch module routed through nafnet_arch_utils.infer_fwd (it answers infer_spec()).  `max_graphs`: how many captured
     forwards (one per input shapes / dtype / kernels.MATH) are kept, least recently used evicted first; 0 = packed weights only, every
     call eager.
 
     Per key the first call runs eagerly under the session's pack plan (the warm-up a capture needs: workspaces and tables are allocated
-    outside it), the second captures and replays, later ones replay.  The result is always a fresh tensor.
+    outside it), the second captures and replays, later ones replay.  The result is always a fresh tensor -- for a network with a
+    list-valued forward (SFNet: three scales) a list of fresh tensors; run_u8 converts the full-size one, the last.
 
     STALENESS IS THE CALLER'S BUSINESS.  The packs are made at construction and by refresh(), never in between: a session cannot see
     that a weight changed in place -- FusedClipAdamW and tdr_multi_ema write parameters through raw pointers, `tensor._version` does not
@@ -98,7 +137,8 @@ class InferenceSession:
     def _build(self):
         self._drop_graphs()
         self.warm.clear()
-        self.ptrs, self.math = pointer_tuple(self.net), K.MATH
+        self.slots = tensor_slots(self.net)
+        self.ptrs, self.math = slot_pointers(self.slots), K.MATH
         self.plan = K.PackPlan(admit=self.ptrs)
         self._repack()
         self.rebuilds += 1
@@ -108,8 +148,10 @@ class InferenceSession:
         self.plan.valid = True                   # whatever is recorded later is packed on the spot from the weights as they are
 
     def stale(self):
-        """what the session can detect on its own: moved parameters / buffers, another arithmetic"""
-        return pointer_tuple(self.net) != self.ptrs or K.MATH != self.math
+        """what the session can detect on its own: moved parameters / buffers, another arithmetic.  Checked on every call, so it reads the
+        slots recorded by _build (tensor_slots) instead of walking the module tree again; a sub-module added or removed after
+        construction is therefore not noticed -- build a new session for another network."""
+        return slot_pointers(self.slots) != self.ptrs or K.MATH != self.math
 
     def refresh(self):
         """the weights changed in place: re-pack all of them (one multi-tensor launch).  Graphs stay -- they read the pack buffers."""
@@ -151,7 +193,7 @@ class InferenceSession:
             return self._forward(images)
         bgr = tag[1]
         planes = [K.img_u8_to_planes(t, swap_rb=bgr) if t is not None and t.dtype == torch.uint8 else t for t in images]
-        return K.planes_to_img_u8(self._forward(planes).contiguous(), swap_rb=bgr)
+        return K.planes_to_img_u8(full_size(self._forward(planes)).contiguous(), swap_rb=bgr)
 
     def _capture(self, images, tag):
         old = self.graphs.make_room()
@@ -191,7 +233,7 @@ class InferenceSession:
                     dst.copy_(src, non_blocking=True)
         ent['graph'].replay()
         self.replays += 1
-        return ent['out'].clone()                # the next replay overwrites the static output
+        return clone_out(ent['out'])             # the next replay overwrites the static output(s)
 
     def __call__(self, *images):
         return self._run(images, None)

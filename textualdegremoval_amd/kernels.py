@@ -2337,6 +2337,14 @@ def gelu_fwd(x, bias=None):
     return z, y
 
 
+def gelu_(x, bias=None):
+    """x <- gelu(x + bias[channel]) in place (a forward pass that keeps no pre-activation); x [N, C, H, W] contiguous.  Returns x."""
+    N, Cc, H, W = x.shape
+    assert x.is_contiguous()
+    check(_lib.load().tdr_gelu_fwd(x.data_ptr(), _p(bias), Cc, H * W, 0, x.data_ptr(), x.numel(), _stream()), 'tdr_gelu_fwd')
+    return x
+
+
 def gelu_bwd(dy, z):
     dz = torch.empty_like(z)
     check(_lib.load().tdr_gelu_bwd(dy.data_ptr(), z.data_ptr(), dz.data_ptr(), z.numel(), _stream()), 'tdr_gelu_bwd')
@@ -2394,6 +2402,47 @@ def region_affine_bwd(dy, x, ph, pl, shift, mean, q, dx):
                                             float(shift), mean.data_ptr(), q, N, Cc, H, W, dx.data_ptr(), _dense_nchw(dx), dph.data_ptr(),
                                             dpl.data_ptr(), ws.data_ptr(), _stream()), 'tdr_region_affine_bwd')
     return dph, dpl
+
+
+SF_REGION_CHUNK_ELEMS = 4096          # what one workgroup of tdr_sf_act_region_sums / _apply covers: 16 elements (4 float4) a thread
+
+
+def sf_region_chunks(H, W, rows_per_chunk=None):
+    """-> (rows_per_chunk, chunks): how the H / 2 rows of a quadrant of an [H, W] plane are cut into row chunks, one workgroup each.
+    A pure function of (H, W): about SF_REGION_CHUNK_ELEMS elements a chunk, the rows spread evenly over the chunks; an explicit
+    `rows_per_chunk` is taken as it is (the last chunk may be ragged)."""
+    qh, qw = H // 2, W // 2
+    if H % 2 or W % 2 or qh < 1 or qw < 1:
+        raise ValueError(f'sf_region_chunks: H and W must be even and >= 2, got {H} x {W}')
+    if rows_per_chunk is None:
+        rows = min(qh, max(1, SF_REGION_CHUNK_ELEMS // qw))
+        rows = -(-qh // -(-qh // rows))                  # the same number of chunks, evened out
+    else:
+        rows = int(rows_per_chunk)
+        if rows < 1:
+            raise ValueError('sf_region_chunks: rows_per_chunk must be >= 1')
+        rows = min(rows, qh)
+    return rows, -(-qh // rows)
+
+
+def sf_act_region_affine(z, gap_h, gap_d, pa_h, pa_l, act, out=None, rows_per_chunk=None, part=None):
+    """forward only: out = region_affine(v) with v = gelu(z) (act = 1) or z (act = 0), Gap (fscale_h, fscale_d) on channels [0, C/2) and
+    Patch_ap (h, l) on [C/2, C) -- two launches over quadrant tiles, no `v` tensor in between (tdr_sf_act_region_sums / _apply).
+    z [N, C, H, W] contiguous; out: like z (may be z itself; allocated when None).  part: the [N * C, 4, chunks] partial sums (scratch)."""
+    N, Cc, H, W = z.shape
+    assert z.is_contiguous() and z.dtype == torch.float32
+    out = torch.empty_like(z) if out is None else out
+    assert out.is_contiguous() and out.shape == z.shape and out.dtype == torch.float32
+    rows, chunks = sf_region_chunks(H, W, rows_per_chunk)
+    if part is None:
+        part = torch.empty(N * Cc * 4 * chunks, dtype=torch.float32, device=z.device)
+    assert part.is_contiguous() and part.numel() >= N * Cc * 4 * chunks and part.dtype == torch.float32
+    lib = _lib.load()
+    check(lib.tdr_sf_act_region_sums(z.data_ptr(), N, Cc, H, W, rows, chunks, int(act), part.data_ptr(), _stream()), 'tdr_sf_act_region_sums')
+    check(lib.tdr_sf_act_region_apply(z.data_ptr(), gap_h.data_ptr(), gap_d.data_ptr(), pa_h.data_ptr(), pa_l.data_ptr(), part.data_ptr(), N, Cc,
+                                      H, W, rows, chunks, int(act), out.data_ptr(), _stream()), 'tdr_sf_act_region_apply')
+    return out
+
 
 def sf_region_split(x, q):
     """the q x q region planes of a dense-NCHW view as a contiguous [N, C q q, H / q, W / q] tensor (q = 1: a dense copy of a channel slice)"""
@@ -2486,13 +2535,13 @@ def sf_dyn_vec_bwd(dtaps, dah, dal, P, pre, k, saved, groups=8):
     return dap, G
 
 
-def sf_dynfilt_fwd(x, taps, ah, al, k, groups=8):
-    """x: dense-NCHW view -> (low, mix) dense [N, C, H, W]"""
+def sf_dynfilt_fwd(x, taps, ah, al, k, groups=8, want_low=True):
+    """x: dense-NCHW view -> (low, mix) dense [N, C, H, W]; want_low=False: (None, mix), the low plane is not written (same mix)"""
     N, Cc, H, W = x.shape
-    low = torch.empty(N, Cc, H, W, dtype=torch.float32, device=x.device)
-    mix = torch.empty_like(low)
+    low = torch.empty(N, Cc, H, W, dtype=torch.float32, device=x.device) if want_low else None
+    mix = torch.empty(N, Cc, H, W, dtype=torch.float32, device=x.device)
     check(_lib.load().tdr_sf_dynfilt_fwd(x.data_ptr(), _dense_nchw(x), taps.data_ptr(), ah.data_ptr(), al.data_ptr(), N, Cc, groups, H, W, k,
-                                         low.data_ptr(), mix.data_ptr(), _stream()), 'tdr_sf_dynfilt_fwd')
+                                         _p(low), mix.data_ptr(), _stream()), 'tdr_sf_dynfilt_fwd')
     return low, mix
 
 

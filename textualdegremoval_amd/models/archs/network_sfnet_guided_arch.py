@@ -121,19 +121,34 @@ class SFNet(nn.Module):
         self.FAM2 = _fam(2 * b)
         self.SCM2 = _scm(2 * b)
 
+    def infer_spec(self):
+        """(fwd, names, params, cfg) of the forward-only route (nafnet_arch_utils.infer_spec; inference.InferenceSession):
+        fwd(P, cfg, x, keep=False) -> ([out 1/4, out 1/2, out full], None).  names / params: the parameters followed by the BUFFERS -- the
+        walk reads the BatchNorm running statistics from P, and a session watches / admits them with the parameters.  Only after .eval():
+        the batch-statistics network moves its buffers on every call, which a captured graph would replay."""
+        if self.training:
+            raise ValueError('SFNet.infer_spec: the forward-only route is the network after .eval() (in training mode BatchNorm2d runs on '
+                             'batch statistics and moves its running buffers)')
+        from ... import sfnet_engine as SE
+        named = list(self.named_parameters()) + list(self.named_buffers())
+
+        def fwd(P, cfg, x, keep=False):
+            return SE.net_fwd(P, x, cfg['num_res'], training=False, tlsc=cfg['tlsc'], keep=keep)
+        return fwd, [k for k, _ in named], [t for _, t in named], dict(num_res=self.num_res, tlsc=self.tlsc)
+
     def forward(self, x):
         """-> [out at 1/4, out at 1/2, out at full size] (reference :366-407); H and W multiples of 8 (two stride-2 levels, quadrants)"""
         if x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError('SFNet: image height and width must be multiples of 8')
+        if not self.training:
+            # module.eval() (the trainer's validation pass): BatchNorm2d on its running statistics, no buffer moves; forward only, nothing
+            # saved (sfnet_engine.net_infer) -- the outputs carry no autograd graph (validation runs under torch.no_grad() in the
+            # reference, base_model / image_restoration_model).  Selected by .eval() alone, whatever the grad mode.
+            fwd, names, params, cfg = self.infer_spec()
+            P = dict(zip(names, [p.detach() for p in params]))
+            return list(fwd(P, cfg, x.detach(), keep=False)[0])
         named = list(self.named_parameters())
         buffers = {k: v for k, v in self.named_buffers()}
-        if not self.training:
-            # module.eval() (the trainer's validation pass): BatchNorm2d on its running statistics, no buffer moves; forward only --
-            # the outputs carry no autograd graph (validation runs under torch.no_grad() in the reference, base_model / image_restoration_model)
-            from ... import sfnet_engine as SE
-            P = {k: p.detach() for k, p in named}
-            P.update(buffers)
-            return list(SE.net_fwd(P, x.detach(), self.num_res, training=False, tlsc=self.tlsc)[0])
         if self.tlsc is not None:
             raise NotImplementedError("SFNet mode 'test' is the reference's inference network: call .eval() first (no training pass is built for it)")
         return list(_SFNetFn.apply(x, self.num_res, [k for k, _ in named], buffers, *[p for _, p in named]))

@@ -6,7 +6,11 @@ Functional like engine.py: parameters and buffers in a dict keyed by the referen
 into libtdr_hip.so: the convolutions on the library's MFMA kernels (engine.conv_fwd / conv_bwd: 3x3 stride 1 / 2, 1x1; the
 4x4 / stride-2 transposed convolutions as 3x3 convolutions to 4 Cout channels + PixelShuffle, csrc/tdr_sfnet.hip), everything around
 them on csrc/tdr_sfnet.hip (GELU, InstanceNorm2d, the Gap / Patch_ap band re-weighting, the dynamic low-pass filter with SFconv).
-The guided class of the same file cannot run in the reference (defect R8); this is the network of that file that does."""
+The guided class of the same file cannot run in the reference (defect R8); this is the network of that file that does.
+`net_fwd(training=False)` -- the network after .eval() -- runs the forward-only walk further down (`net_infer`: nothing saved, GELU in
+place, the fused GELU -> Gap / Patch_ap pair), which is also what inference.InferenceSession packs once and replays."""
+from collections import namedtuple
+
 import torch
 
 from . import engine as E
@@ -65,9 +69,13 @@ _tlsc = None            # mode[0] == 'test': the TLSC base size (246 Indoor / 21
 TLSC_BASE = {'Indoor': 246, 'Outdoor': 210}       # sfnet_arch_utils.py:110-113
 
 
-def _box(x, H, W):
+def _box_of(x, H, W, tlsc):
     """AvgPool2d(base_size) of the reference's test mode on a contiguous [N, C, H, W]: k = size * base // 256 (:33-34), replicate-padded back"""
-    return K.local_avgpool(x, min(H, H * _tlsc // 256), min(W, W * _tlsc // 256))
+    return K.local_avgpool(x, min(H, H * tlsc // 256), min(W, W * tlsc // 256))
+
+
+def _box(x, H, W):
+    return _box_of(x, H, W, _tlsc)
 
 
 def dyn_fwd(x, P, pre, k, out):
@@ -183,14 +191,21 @@ def cat_conv_bwd(dy, P, pre, saved, G):
 
 
 # ------------------------------------------------------------------------------------------------- SFNet.forward (:366-407)
-def net_fwd(P, x, num_res, training=True, tlsc=None):
+def net_fwd(P, x, num_res, training=True, tlsc=None, keep=None):
     """training=False: module.eval() -- BatchNorm2d on its running statistics, buffers untouched (InstanceNorm2d and the global pools are
     the same in both modes: the reference builds them without running statistics, sfnet_arch_utils.py:208, :108).
     tlsc = TLSC_BASE[mode[1]]: the mode[0] == 'test' network -- Gap / Patch_ap / SFconv pool with the box mean of that base size;
-    inference only (nothing is kept for a backward pass)"""
+    inference only (nothing is kept for a backward pass).
+    keep (default: `training`): False -- a forward pass no backward follows (training=False only) -> ([o4, o2, o1], None): the walk of
+    net_infer below, which builds no `saved` tuple.  keep=True with training=False is the eval pass on the training walk."""
     global _training, _tlsc
     if tlsc is not None and training:
         raise ValueError("SFNet mode 'test' is an inference network: training=False")
+    keep = bool(training) if keep is None else bool(keep)
+    if not keep:
+        if training:
+            raise ValueError('SFNet keep=False is a forward-only pass: training=False (a training pass keeps what its backward reads)')
+        return net_infer(P, x, num_res, InferMode(tlsc, INFER_KERNELS)), None
     _training, _tlsc = bool(training), tlsc
     try:
         return _net_fwd(P, x, num_res)
@@ -225,6 +240,115 @@ def _net_fwd(P, x, num_res):
     saved = (num_res, sv_scm2, sv_scm1, sv_f0, sv_e0, sv_f1, sv_fam2, sv_e1, sv_f2, sv_fam1, sv_e2, sv_d0, sv_o0, sv_f3, sv_c0, sv_d1, sv_o1,
              sv_f4, sv_c1, sv_d2, sv_f5)
     return [o4, o2, o1], saved
+
+
+# ------------------------------------------------------------------------------------------------- the forward-only walk (keep=False)
+# module.eval() and inference.InferenceSession: BatchNorm2d on its running statistics, nothing saved -- every intermediate is released
+# behind its last reader --, GELU in place on the convolution output, and per ordinary ResBlock two launches over quadrant tiles
+# (K.sf_act_region_affine) for GELU -> Gap / Patch_ap where the training walk runs three, two of them on (q * q, C / 2, N) workgroups.
+# The mode travels as an argument (no module state): tlsc = the TLSC base size or None, fused = INFER_KERNELS when the walk started.
+INFER_KERNELS = True            # False: gelu_ + region_affine_fwd per op (the bits of the training walk): A/B in profiles/probe_sfnet_infer.py
+InferMode = namedtuple('InferMode', 'tlsc fused')
+
+
+def infer_conv(x, P, pre, k, stride=1, act=True, res=None):
+    if act and res is not None:
+        raise ValueError('infer_conv: a residual goes with act=False (BasicConv has no skip behind its GELU)')
+    z = E.conv_fwd(x, P[pre + 'main.0.weight'], P[pre + 'main.0.bias'], stride, k // 2, res=None if act else res)
+    return K.gelu_(z) if act else z
+
+
+def infer_convt(x, P, pre):
+    w, b = P[pre + 'main.0.weight'], P[pre + 'main.0.bias']
+    w3, _ = K.convt4_weight_to_3x3(w, None)
+    wp, mp, *_ = K.pack_weights(w3, PACK_FWD)            # (derived per call: a session's plan packs it on the spot, never records it)
+    return K.gelu_(K.conv_forward(x, wp, mp, 4 * w.shape[1], 3, pad=1, epi=EPI_PSHUF), bias=b)
+
+
+def infer_dyn(x, P, pre, k, out, mode):
+    """x, out: channel-slice views [N, c, H, W]"""
+    taps, ah, al, _ = K.sf_dyn_vec_fwd(K.plane_mean(x), P, pre, k, GROUPS, training=False)
+    low, mix = K.sf_dynfilt_fwd(x, taps, ah, al, k, GROUPS, want_low=mode.tlsc is not None)
+    if mode.tlsc is not None:
+        H, W = x.shape[2:]
+        z = E.conv_fwd(_box_of(K.sf_emerge(x, low), H, W, mode.tlsc), P[pre + 'modulate.fc.weight'], P[pre + 'modulate.fc.bias'], 1, 0)
+        lh = E.conv_fwd(z, P[pre + 'modulate.fcs.0.weight'], P[pre + 'modulate.fcs.0.bias'], 1, 0)
+        ll = E.conv_fwd(z, P[pre + 'modulate.fcs.1.weight'], P[pre + 'modulate.fcs.1.bias'], 1, 0)
+        mix = K.sf_softmax_mix(x, low, lh, ll)
+    E.conv_fwd(mix, P[pre + 'modulate.out.weight'], P[pre + 'modulate.out.bias'], 1, 0, out=out)
+
+
+def infer_res(x, P, pre, filt, mode):
+    N, C, H, W = x.shape
+    h = C // 2
+    cur = infer_conv(x, P, pre + 'conv1.', 3, act=False)              # z: the GELU comes with the pooling where that is fused
+    gap = (P[pre + 'global_ap.fscale_h'], P[pre + 'global_ap.fscale_d'])
+    pap = (P[pre + 'localap.h'], P[pre + 'localap.l'])
+    fused = mode.fused and mode.tlsc is None
+    if filt or not fused:
+        K.gelu_(cur)
+    if filt:
+        y1, cur = cur, torch.empty_like(cur)
+        infer_dyn(y1[:, :h], P, pre + 'dyna.', 3, cur[:, :h], mode)
+        infer_dyn(y1[:, h:], P, pre + 'dyna_2.', 5, cur[:, h:], mode)
+        del y1
+    if fused:
+        r = K.sf_act_region_affine(cur, *gap, *pap, act=0 if filt else 1, out=cur)
+    else:
+        r = torch.empty_like(cur)
+        if mode.tlsc is not None:
+            K.sf_local_affine(cur[:, :h], _box_of(K.sf_region_split(cur[:, :h], 1), H, W, mode.tlsc), *gap, 1.0, 1, r[:, :h])
+            K.sf_local_affine(cur[:, h:], _box_of(K.sf_region_split(cur[:, h:], 2), H // 2, W // 2, mode.tlsc), *pap, 0.0, 2, r[:, h:])
+        else:
+            K.region_affine_fwd(cur[:, :h], *gap, 1.0, 1, r[:, :h])
+            K.region_affine_fwd(cur[:, h:], *pap, 0.0, 2, r[:, h:])
+    del cur
+    return infer_conv(r, P, pre + 'conv2.', 3, act=False, res=x)
+
+
+def infer_blocks(x, P, pre, num_res, mode):
+    for r in range(num_res):
+        x = infer_res(x, P, f'{pre}layers.{r}.', r == num_res - 1, mode)
+    return x
+
+
+def infer_scm(x, P, pre):
+    x = infer_conv(x, P, pre + 'main.0.', 3)
+    x = infer_conv(x, P, pre + 'main.1.', 1)
+    x = infer_conv(x, P, pre + 'main.2.', 3)
+    x = infer_conv(x, P, pre + 'main.3.', 1, act=False)
+    return K.instnorm_fwd(x, P[pre + 'main.4.weight'], P[pre + 'main.4.bias'])[0]
+
+
+def net_infer(P, x, num_res, mode):
+    """SFNet.forward (:366-407) with nothing kept -> [out 1/4, out 1/2, out full]"""
+    x = x.contiguous()
+    x_2 = K.subsample2(x)
+    x_4 = K.subsample2(x_2)
+    z2 = infer_scm(x_2, P, 'SCM2.')
+    z4 = infer_scm(x_4, P, 'SCM1.')
+    res1 = infer_blocks(infer_conv(x, P, 'feat_extract.0.', 3), P, 'Encoder.0.', num_res, mode)
+    z = infer_conv(res1, P, 'feat_extract.1.', 3, stride=2)
+    z = infer_conv(K.concat2(z, z2), P, 'FAM2.merge.', 3, act=False)
+    del z2
+    res2 = infer_blocks(z, P, 'Encoder.1.', num_res, mode)
+    z = infer_conv(res2, P, 'feat_extract.2.', 3, stride=2)
+    z = infer_conv(K.concat2(z, z4), P, 'FAM1.merge.', 3, act=False)
+    del z4
+    z = infer_blocks(z, P, 'Encoder.2.', num_res, mode)
+    z = infer_blocks(z, P, 'Decoder.0.', num_res, mode)
+    o4 = infer_conv(z, P, 'ConvsOut.0.', 3, act=False, res=x_4)
+    z = infer_convt(z, P, 'feat_extract.3.')
+    z = infer_conv(K.concat2(z, res2), P, 'Convs.0.', 1)
+    del res2
+    z = infer_blocks(z, P, 'Decoder.1.', num_res, mode)
+    o2 = infer_conv(z, P, 'ConvsOut.1.', 3, act=False, res=x_2)
+    z = infer_convt(z, P, 'feat_extract.4.')
+    z = infer_conv(K.concat2(z, res1), P, 'Convs.1.', 1)
+    del res1
+    z = infer_blocks(z, P, 'Decoder.2.', num_res, mode)
+    o1 = infer_conv(z, P, 'feat_extract.5.', 3, act=False, res=x)
+    return [o4, o2, o1]
 
 
 def net_bwd(douts, P, saved, G=None):
