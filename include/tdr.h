@@ -25,8 +25,12 @@ extern "C" {
  * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local; still 112,
  * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8, then
  * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL -- no existing entry point
- * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there); the
- * binding (textualdegremoval_amd/_lib.py) refuses a library whose version differs from the one it was written against. */
+ * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there).
+ * This header is the only written copy of the ABI: the binding (textualdegremoval_amd/_lib.py) derives its ctypes structs, argument lists and
+ * version number from the text below at import and refuses a library whose tdr_version() differs.  Its parser knows the C this file uses and
+ * nothing more -- prototypes, `typedef struct X {...} X;`, opaque `typedef struct X X;`; `int`, `int64_t`, `float` by value; pointers to those,
+ * to `void` / `char` / `unsigned` / `uint8_t` / `double` and to the structs declared here -- and stops the import at anything else
+ * (tests/test_cabi_binding_host.py).  A struct that lives in device memory and is passed by address goes into its _DEVICE_STRUCT_PARAMS. */
 #define TDR_ABI_VERSION 112
 int tdr_version(void);
 const char* tdr_last_error(void);
