@@ -24,7 +24,8 @@ extern "C" {
  * round 5, 105 - 107 round 6: the SFNet operators, their inference modes, the table-driven finishing reductions; 108: the
  * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local; still 112,
  * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8, then
- * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL -- no existing entry point
+ * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL, then tdr_tile_gather /
+ * tdr_tile_blend -- no existing entry point
  * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there).
  * This header is the only written copy of the ABI: the binding (textualdegremoval_amd/_lib.py) derives its ctypes structs, argument lists and
  * version number from the text below at import and refuses a library whose tdr_version() differs.  Its parser knows the C this file uses and
@@ -439,6 +440,23 @@ int tdr_niqe_features(const float* y, int H, int W, int block, const double* win
  *     img = uint8(rint(min(max(v, 0), 1) * 255.0f)) -- float32 product, round half to even.  Finite inputs. */
 int tdr_img_u8_to_planes(const uint8_t* img, int N, int H, int W, int C, int swap_rb, float* out, int Hp, int Wp, void* stream);
 int tdr_planes_to_img_u8(const float* in, int N, int C, int Hp, int Wp, int swap_rb, uint8_t* img, int H, int W, void* stream);
+/* Tiled inference (csrc/tdr_tile.hip; an addition to ABI 112): an image of any size through the forward of one tile shape -- the `grids` /
+ * tile testing of the upstream NAFNet and Restormer test code; the plan (starts, weights, batches) is the caller's, inference.py.
+ *   tdr_tile_gather: one batch of B tiles of th x tw out of N images.  src: float32 [N][C][H][W] (src_u8 = 0; swap_rb ignored), or uint8
+ *     [N][H][W][C], C in {1, 3, 6}, as cv2 decodes (src_u8 = 1): converted as tdr_img_u8_to_planes converts -- the same 256-entry table of
+ *     float32(u) / 255.0f, channels 0 and 2 of a 3-channel image exchanged when swap_rb.  table: int32 [B][3] in device memory, (n, y0, x0)
+ *     per tile; out: float32 [B][C][th][tw].  A tile must lie inside its image; an entry that does not yields zeros, nothing outside
+ *     the images is read.
+ *   tdr_tile_blend: out [N][C][H][W] from tiles [N * ny * nx][C][th][tw] (image-major, then row-major).  Per dimension of length L (y: H,
+ *     ny tiles of th; x: W, nx tiles of tw) three device tables: start int32 [n] (where each tile begins), idx int32 [L][2] (per pixel
+ *     the first covering tile and how many cover it -- a contiguous range) and w float32 [L][K] (their weights, K the widest cover).
+ *     out[n][c][y][x] = sum over a < cnt_y (outside), b < cnt_x (inside) of (wy[a] * wx[b]) * tiles[(n ny + first_y + a) nx + first_x + b]
+ *     [c][y - start_y][x - start_x], fp32 in that fixed order, no contraction, no atomics: deterministic, and a pixel that one tile covers
+ *     with weight 1.0f is a bit-exact copy.  A term whose tile index or offset is out of range is left out. */
+int tdr_tile_gather(const void* src, int src_u8, int N, int C, int H, int W, int swap_rb, const int* table, int B, int th, int tw,
+                    float* out, void* stream);
+int tdr_tile_blend(const float* tiles, int N, int C, int H, int W, int th, int tw, int ny, int nx, const int* ystart, const int* yidx,
+                   const float* yw, int Ky, const int* xstart, const int* xidx, const float* xw, int Kx, float* out, void* stream);
 
 /* TLSC local average pooling -- `AvgPool2d.forward` of models/archs/nafnet_local_arch.py:10-75 (fast_imp = False, auto_pad):
  * out[p][y][x] = mean of the k1' x k2' box (k' = min(size, k)) whose top-left corner is (clamp(y - (H - hv) / 2, 0, hv - 1),

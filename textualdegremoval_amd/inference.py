@@ -7,10 +7,13 @@ validation set.  A session packs the network's weights once and replays the forw
     out = sess(lq, ref)            # the positional images of net.forward (NAFNetDynamicFusion: (lq, k_v)); bit-identical to it
     sess.refresh()                 # the weights changed in place: re-pack (one launch), keep the graphs
     sess.release()                 # drop graphs, their pool, the packs
+    out = sess.run_tiled(lq, ref, tile=256, overlap=32, tile_batch=4)      # an image of any size through the graph of ONE tile shape
 
-The host-side bookkeeping (GraphLRU, session_key, what makes a session stale) needs no GPU and is tested without one."""
+The host-side bookkeeping (GraphLRU, session_key, what makes a session stale, the tile plan: tile_starts / tile_weights / tile_batches)
+needs no GPU and is tested without one."""
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from . import kernels as K
@@ -100,6 +103,74 @@ def full_size(out):
     return out[-1] if isinstance(out, (list, tuple)) else out
 
 
+# ---- the tile plan of run_tiled: where the tiles of one dimension start, how the tiles covering a pixel are weighted, how the tiles of
+# a call are chunked into batches of one size
+def tile_starts(L, tile, overlap):
+    """the tiles of a dimension of length L -> (starts, t): t = min(tile, L) is their common length; one tile at 0 where L <= t, else
+    0, s, 2s, ... (s = t - overlap) while i * s < L - t, then a last one clamped to the border at L - t"""
+    L, tile, overlap = int(L), int(tile), int(overlap)
+    if L <= 0 or tile <= 0 or overlap < 0 or overlap >= tile:
+        raise ValueError(f'tile_starts: length {L}, tile {tile}, overlap {overlap} (want L > 0, tile > 0, 0 <= overlap < tile)')
+    t = min(tile, L)
+    if L <= t:
+        return [0], t
+    return list(range(0, L - t, t - overlap)) + [L - t], t
+
+
+def tile_weights(L, tile, overlap):
+    """the blend table of a dimension, a row per pixel y -> (first int32 [L], cnt int32 [L], w float32 [L, K]): the tiles covering y are
+    first[y] ... first[y] + cnt[y] - 1 (always a contiguous range), w[y, a] the weight of the a-th of them, 0 for a >= cnt[y]; K = max cnt
+    (not bounded by 2: the clamped last tile may lie over two others).  Tile i weighs r = min(j + 1, t - j, overlap + 1) at its offset
+    j = y - starts[i] -- a ramp over the overlap, flat inside; normalised over the covering tiles in float64 (the sums are whole numbers),
+    then cast: a pixel covered once weighs exactly 1.0f, and with overlap = 0 every weight is 1.0f"""
+    starts, t = tile_starts(L, tile, overlap)
+    j = np.arange(int(L), dtype=np.int64)[:, None] - np.asarray(starts, dtype=np.int64)[None, :]
+    cover = (j >= 0) & (j < t)
+    r = np.where(cover, np.minimum(np.minimum(j + 1, t - j), int(overlap) + 1), 0)
+    first, cnt = cover.argmax(axis=1), cover.sum(axis=1)
+    norm = r.astype(np.float64) / r.sum(axis=1, keepdims=True).astype(np.float64)
+    w = np.zeros((int(L), int(cnt.max())), np.float32)
+    for a in range(w.shape[1]):
+        rows = np.nonzero(a < cnt)[0]
+        w[rows, a] = norm[rows, first[rows] + a].astype(np.float32)
+    return first.astype(np.int32), cnt.astype(np.int32), w
+
+
+def tile_batches(n_tiles, tile_batch):
+    """the tile indices 0 ... n_tiles - 1 (all images of a call: image-major, then row-major) in chunks of exactly `tile_batch`; the last
+    chunk is padded by repeating its last tile, so every forward of a call -- and of every later image size -- has one shape"""
+    n_tiles, tile_batch = int(n_tiles), int(tile_batch)
+    if n_tiles <= 0 or tile_batch <= 0:
+        raise ValueError(f'tile_batches: {n_tiles} tiles in batches of {tile_batch}')
+    idx = list(range(n_tiles)) + [n_tiles - 1] * (-n_tiles % tile_batch)
+    return [idx[k:k + tile_batch] for k in range(0, len(idx), tile_batch)]
+
+
+class TilePlan:
+    """the device tables of one (N, H, W, tile, overlap, tile_batch): a single int32 buffer (one host-to-device copy), cut into the
+    gather table [T', 3] of (n, y0, x0) per padded tile slot, the image index [T'] of every slot, and per dimension start [n], idx [L, 2]
+    and the weights [L, K] (float32 bits)"""
+
+    def __init__(self, N, H, W, tile, overlap, tile_batch, device):
+        ys, self.th = tile_starts(H, tile[0], overlap)
+        xs, self.tw = tile_starts(W, tile[1], overlap)
+        self.ny, self.nx, self.n_tiles, self.tile_batch = len(ys), len(xs), N * len(ys) * len(xs), int(tile_batch)
+        self.batches = tile_batches(self.n_tiles, tile_batch)
+        slots = np.asarray(self.batches, dtype=np.int64).ravel()
+        n, rem = slots // (self.ny * self.nx), slots % (self.ny * self.nx)
+        table = np.stack([n, np.asarray(ys)[rem // self.nx], np.asarray(xs)[rem % self.nx]], axis=1).astype(np.int32)
+        parts = [table.ravel(), n.astype(np.int32)]
+        for L, starts, t in ((H, ys, tile[0]), (W, xs, tile[1])):    # (the tile as asked for: `overlap` may exceed a clamped one)
+            first, cnt, w = tile_weights(L, t, overlap)
+            parts += [np.asarray(starts, dtype=np.int32), np.stack([first, cnt], axis=1).ravel(), w.ravel().view(np.int32)]
+        cuts = np.cumsum([0] + [p.size for p in parts])
+        dev = torch.from_numpy(np.concatenate(parts)).to(device)
+        cut = [dev[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        self.table, self.image = cut[0].view(-1, 3), cut[1]
+        self.ytabs = (cut[2], cut[3].view(H, 2), cut[4].view(torch.float32).view(H, -1))
+        self.xtabs = (cut[5], cut[6].view(W, 2), cut[7].view(torch.float32).view(W, -1))
+
+
 class InferenceSession:
     """`net`: any arch module routed through nafnet_arch_utils.infer_fwd (it answers infer_spec()).  `max_graphs`: how many captured
     forwards (one per input shapes / dtype / kernels.MATH) are kept, least recently used evicted first; 0 = packed weights only, every
@@ -118,7 +189,12 @@ class InferenceSession:
 
     The plan admits parameters and buffers of `net` only (kernels.PackPlan(admit=)): weights a forward derives per call are packed on
     the spot -- inside the graph once captured -- and never recorded, so `len(sess.plan.entries)` stops growing after the first call of a
-    shape."""
+    shape.
+
+    run_tiled / run_tiled_u8 cut images of any size into overlapping tiles of one size, run the tiles through the forward in batches of
+    one size -- one key, one graph, whatever sizes follow -- and blend the tile outputs (see run_tiled)."""
+
+    TILE_PLANS = 32                              # device tables kept for repeated (N, H, W, tile, overlap, tile_batch)
 
     def __init__(self, net, max_graphs=4):
         if max_graphs < 0:
@@ -131,6 +207,7 @@ class InferenceSession:
         self.plan = None
         self.released = False
         self.captures = self.replays = self.rebuilds = 0
+        self.tile_plans = OrderedDict()
         self._build()
 
     # ---- weights
@@ -165,6 +242,7 @@ class InferenceSession:
         self._drop_graphs()
         self.warm.clear()
         self.plan = self.pool = None
+        self.tile_plans.clear()
         self.released = True
 
     def _alive(self):
@@ -213,7 +291,9 @@ class InferenceSession:
         self.captures += 1
         return ent
 
-    def _run(self, images, tag):
+    def _run(self, images, tag, take=None):
+        """`take`: what becomes of the output instead of the default (the eager forward's own tensors / a clone of the captured entry's
+        static ones): called with the output, its result returned -- run_tiled copies a replay's static output once, into the tile buffer"""
         self._alive()
         if self.stale():
             self._build()
@@ -222,7 +302,8 @@ class InferenceSession:
         key = session_key(images, K.MATH, tag)
         if self.max_graphs == 0 or key not in self.warm:
             self.warm.add(key)
-            return self._body(images, tag)
+            out = self._body(images, tag)
+            return out if take is None else take(out)
         ent = self.graphs.get(key)
         if ent is None:
             ent = self._capture(images, tag)
@@ -233,7 +314,7 @@ class InferenceSession:
                     dst.copy_(src, non_blocking=True)
         ent['graph'].replay()
         self.replays += 1
-        return clone_out(ent['out'])             # the next replay overwrites the static output(s)
+        return (clone_out if take is None else take)(ent['out'])      # the next replay overwrites the static output(s)
 
     def __call__(self, *images):
         return self._run(images, None)
@@ -247,3 +328,79 @@ class InferenceSession:
         if lq_u8.dtype != torch.uint8:
             raise TypeError('run_u8: lq_u8 must be a uint8 [N,H,W,C] tensor')
         return self._run(images, ('u8', bool(bgr)))
+
+    # ---- tiled
+    def _tile_plan(self, N, H, W, tile, overlap, tile_batch, device):
+        th, tw = (tile, tile) if isinstance(tile, int) else tile
+        tile = (int(th), int(tw))
+        key = (N, H, W, tile_starts(H, th, overlap)[1], tile_starts(W, tw, overlap)[1], int(overlap), int(tile_batch), str(device))
+        plan = self.tile_plans.get(key)
+        if plan is None:
+            while len(self.tile_plans) >= self.TILE_PLANS:
+                self.tile_plans.popitem(last=False)
+            plan = self.tile_plans[key] = TilePlan(N, H, W, tile, int(overlap), int(tile_batch), device)
+        else:
+            self.tile_plans.move_to_end(key)
+        return plan
+
+    def _tiled(self, src, extra, tile, overlap, tile_batch, swap_rb):
+        self._alive()
+        require_gpu(src, type(self.net).__name__)
+        src = src.contiguous()
+        N, H, W = (src.shape[0], src.shape[1], src.shape[2]) if src.dtype == torch.uint8 else (src.shape[0], src.shape[2], src.shape[3])
+        for e in extra:
+            if e is not None and e.shape[0] != N:
+                raise ValueError(f'run_tiled: an extra input of {e.shape[0]} rows for {N} images')
+        plan = self._tile_plan(N, H, W, tile, overlap, tile_batch, src.device)
+        B, held = plan.tile_batch, []
+
+        def take(out):
+            full = full_size(out)
+            if full.dim() != 4 or tuple(full.shape[2:]) != (plan.th, plan.tw):
+                raise NotImplementedError(f'run_tiled: {type(self.net).__name__} answers {tuple(full.shape)} to tiles of {plan.th} x {plan.tw}; '
+                                          'only networks of scale 1 are tiled')
+            if not held:
+                held.append(torch.empty(plan.n_tiles, full.shape[1], plan.th, plan.tw, dtype=torch.float32, device=full.device))
+            real = min(B, plan.n_tiles - k * B)                  # (the padding slots of the last batch are dropped)
+            held[0][k * B:k * B + real].copy_(full[:real])
+
+        for k in range(len(plan.batches)):
+            tiles = K.tile_gather(src, plan.table[k * B:(k + 1) * B], plan.th, plan.tw, swap_rb=swap_rb)
+            rows = plan.image[k * B:(k + 1) * B]
+            self._run((tiles,) + tuple(e if e is None else e.index_select(0, rows) for e in extra), None, take)
+        return K.tile_blend(held[0], N, H, W, plan.ytabs, plan.xtabs)
+
+    def run_tiled(self, lq, *extra, tile=256, overlap=32, tile_batch=4):
+        """lq float32 [N,C,H,W] of ANY size -> float32 [N,C_out,H,W], through forwards of one shape: the image is cut into tiles of `tile`
+        (an int or (th, tw); min(tile, image) per dimension) that overlap by `overlap` pixels, the last tile of a row / column clamped
+        to the border (tile_starts); the tiles of all N images run through the network in batches of exactly `tile_batch` (the last batch
+        padded with a repeated tile, tile_batches) -- every batch through the same pack plan and warm / capture / replay ladder as
+        `sess(...)`, under ONE key (tile_batch, C, th, tw) whatever image sizes follow: one capture serves a validation folder of many
+        sizes; with max_graphs=0 the batches run eagerly.  The outputs are blended with weights that ramp linearly over the overlap
+        (tile_weights), one deterministic gather launch (kernels.tile_blend).
+
+        `extra`: the other positional inputs of the network's forward -- ref [N,3,Hr,Wr] of the RefFusion classes, k_v [N,10,1024] of
+        NAFNetDynamicFusion.  They are never tiled: row n accompanies every tile of image n (index_select, a copy).
+
+        THE RESULT IS THE BLEND OF INDEPENDENT FORWARDS OF THE TILES, NOT THE FULL-FRAME FORWARD: whatever a block pools over the image
+        (SCA, MDTA's channel attention, InstanceNorm) it pools per tile -- that is the point: a network trained on patches of `tile`
+        sees the statistics it was trained on (`grids` / tile testing of the upstream NAFNet and Restormer test code).  It is the same
+        computation as sess(lq), and gives its bits, only for tile >= image, tile_batch=1, N=1.  A list-valued forward (SFNet)
+        contributes its full-size output, the last.  Scale-1 networks only (NotImplementedError otherwise).
+
+        The device tables of a plan are kept per (N, H, W, th, tw, overlap, tile_batch) (the gather table holds the padding of the
+        last batch, hence tile_batch), at most TILE_PLANS of them: a repeated image size copies nothing to the device."""
+        if lq.dtype != torch.float32 or lq.dim() != 4:
+            raise TypeError('run_tiled: lq must be a float32 [N,C,H,W] tensor')
+        return self._tiled(lq, extra, tile, overlap, tile_batch, False)
+
+    def run_tiled_u8(self, lq_u8, extra=None, tile=256, overlap=32, tile_batch=4, bgr=True):
+        """run_tiled on bytes: lq_u8 uint8 [N,H,W,C] as cv2 decodes it -> uint8 [N,H,W,C].  The tiles are gathered straight from the bytes
+        (converted as kernels.img_u8_to_planes converts, `bgr` exchanging channels 0 and 2 on the way in and back), the blended planes go
+        through kernels.planes_to_img_u8: bit for bit planes_to_img_u8(run_tiled(img_u8_to_planes(lq_u8))), on the same graph.
+        `extra`: None, one tensor or a sequence; a uint8 one (a ref image [N,Hr,Wr,3]) is converted once per call, not once per tile."""
+        if lq_u8.dtype != torch.uint8 or lq_u8.dim() != 4:
+            raise TypeError('run_tiled_u8: lq_u8 must be a uint8 [N,H,W,C] tensor')
+        extra = () if extra is None else (extra,) if torch.is_tensor(extra) else tuple(extra)
+        extra = tuple(K.img_u8_to_planes(e.contiguous(), swap_rb=bgr) if e is not None and e.dtype == torch.uint8 else e for e in extra)
+        return K.planes_to_img_u8(self._tiled(lq_u8, extra, tile, overlap, tile_batch, bool(bgr)), swap_rb=bgr)

@@ -1314,6 +1314,38 @@ def planes_to_img_u8(x, H=None, W=None, swap_rb=True):
     return out
 
 
+def tile_gather(src, table, th, tw, swap_rb=True):
+    """one batch of tiles out of the images: src float32 [N,C,H,W] or uint8 [N,H,W,C] (C in {1, 3, 6}; converted as img_u8_to_planes
+    converts, `swap_rb` included -- ignored for a float source), table int32 [B,3] on the device, (n, y0, x0) per tile -> float32
+    [B,C,th,tw], one launch (csrc/tdr_tile.hip)"""
+    u8 = src.dtype == torch.uint8
+    assert (u8 or src.dtype == torch.float32) and src.dim() == 4 and src.is_contiguous()
+    assert table.dtype == torch.int32 and table.dim() == 2 and table.shape[1] == 3 and table.is_contiguous() and table.device == src.device
+    N, Cc, H, W = (src.shape[0], src.shape[3], src.shape[1], src.shape[2]) if u8 else src.shape
+    out = torch.empty(table.shape[0], Cc, int(th), int(tw), dtype=torch.float32, device=src.device)
+    check(_lib.load().tdr_tile_gather(src.data_ptr(), int(u8), N, Cc, H, W, int(bool(swap_rb)), table.data_ptr(), table.shape[0], int(th),
+                                      int(tw), out.data_ptr(), _stream()), 'tdr_tile_gather')
+    return out
+
+
+def tile_blend(tiles, N, H, W, ytabs, xtabs):
+    """the images of a tiled run from all its tile outputs: tiles float32 [N * ny * nx, C, th, tw] (image-major, then row-major), per
+    dimension the device tables (start int32 [n], idx int32 [L,2], w float32 [L,K]) of inference.tile_weights -> float32 [N,C,H,W]:
+    per pixel the weighted sum over its covering tiles in a fixed fp32 order, one launch, no atomics (csrc/tdr_tile.hip)"""
+    assert tiles.dtype == torch.float32 and tiles.dim() == 4 and tiles.is_contiguous()
+    (ys, yi, yw), (xs, xi, xw) = ytabs, xtabs
+    for L, (s, i, w) in ((H, ytabs), (W, xtabs)):
+        assert s.dtype == i.dtype == torch.int32 and w.dtype == torch.float32 and s.is_contiguous() and i.is_contiguous() and w.is_contiguous()
+        assert i.shape == (L, 2) and w.dim() == 2 and w.shape[0] == L and s.dim() == 1
+    T, Cc, th, tw = tiles.shape
+    ny, nx = ys.shape[0], xs.shape[0]
+    assert T == N * ny * nx, (T, N, ny, nx)
+    out = torch.empty(N, Cc, H, W, dtype=torch.float32, device=tiles.device)
+    check(_lib.load().tdr_tile_blend(tiles.data_ptr(), N, Cc, H, W, th, tw, ny, nx, ys.data_ptr(), yi.data_ptr(), yw.data_ptr(), yw.shape[1],
+                                     xs.data_ptr(), xi.data_ptr(), xw.data_ptr(), xw.shape[1], out.data_ptr(), _stream()), 'tdr_tile_blend')
+    return out
+
+
 def relu_bwd(go, act):
     assert go.is_contiguous() and act.is_contiguous()
     out = torch.empty_like(go)

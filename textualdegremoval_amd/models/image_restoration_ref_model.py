@@ -440,7 +440,14 @@ class RefGuidedImageCleanModel(BaseModel):
         img = self.lq if img is None else img
         net = self.net_g_ema if hasattr(self, 'net_g_ema') else self.net_g
         net.eval()
-        if (self.opt.get('val') or {}).get('session', False):
+        val = self.opt.get('val') or {}
+        if val.get('tile'):
+            # `val: {tile: 256, tile_overlap: 32, tile_batch: 4}`: every image, whatever its size, as overlapping tiles of the training
+            # patch size through one captured graph (InferenceSession.run_tiled); implies the validation session
+            tile = val['tile']
+            pred = self._val_session(net).run_tiled(img, self.ref, tile=tile if isinstance(tile, int) else tuple(tile),
+                                                    overlap=val.get('tile_overlap', 32), tile_batch=val.get('tile_batch', 4))
+        elif val.get('session', False):
             pred = self._val_session(net)(img, self.ref)
         else:
             with torch.no_grad():
