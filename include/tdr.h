@@ -25,7 +25,7 @@ extern "C" {
  * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local; still 112,
  * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8, then
  * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL, then tdr_tile_gather /
- * tdr_tile_blend -- no existing entry point
+ * tdr_tile_blend, then tdr_window_resize_bilinear / tdr_token_match_bank -- no existing entry point
  * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there).
  * This header is the only written copy of the ABI: the binding (textualdegremoval_amd/_lib.py) derives its ctypes structs, argument lists and
  * version number from the text below at import and refuses a library whose tdr_version() differs.  Its parser knows the C this file uses and
@@ -626,6 +626,19 @@ int tdr_attention_fwd_math(const float* qkv, int B, int C, int heads, int T, int
  * fl [B][D][LD], fr [B*N][D][LD], windows [B*N][per] -> corr [B][N], index [B] (int32), ref_in [B][per] (:230-243) */
 int tdr_token_match(const float* fl, const float* fr, const float* windows, int B, int N, int D, int T1, int LD, int64_t per,
                     float* corr, int* index, float* ref_in, void* stream);
+/* Matched tiled inference (an addition to ABI 112): the window features of a ref are computed once per image (the "bank"), every tile of
+ * that image is matched against them.  Windows as tdr_unfold_windows numbers them: n = wy*nx + wx, ny = (Hr - t)/stride + 1, nx likewise.
+ *   tdr_window_resize_bilinear: windows n0 .. n0 + count - 1 of every image, resized -> dst [B*count][C][Hd][Wd] (image-major), read in
+ *     place from ref [B][C][Hr][Wr]: the bits of tdr_resize_bilinear over those windows of tdr_unfold_windows, without that tensor.
+ *   tdr_token_match_bank: fl [Bt][D][LD] (the tiles), bank [Nimg*Nw][D][LD], rows int32 [Bt] in device memory (the image of each slot)
+ *     -> corr [Bt][Nw], index [Bt], ref_in [Bt][C][t][t] gathered from ref [Nimg][C][Hr][Wr].  Per slot the additions of tdr_token_match
+ *     in its order (the same bits); a bank slice is read once for all slots of its image.  ws: Bt*Nw*48*3 floats (the partials).  A slot
+ *     whose row is outside [0, Nimg) gets corr 0, index -1 and zeros.  LD % 4 == 0. */
+int tdr_window_resize_bilinear(const float* ref, int B, int C, int Hr, int Wr, int t, int stride, int n0, int count, float* dst, int Hd,
+                               int Wd, void* stream);
+int tdr_token_match_bank(const float* fl, const float* bank, const int* rows, const float* ref, int Bt, int Nimg, int Nw, int D, int T1,
+                         int LD, int C, int Hr, int Wr, int t, int stride, int nx, float* ws, float* corr, int* index, float* ref_in,
+                         void* stream);
 
 /* Token-major fp16 pipeline of the frozen DINOv2 matcher (csrc/tdr_tok16.hip; replaces the per-block calls of
  * models/dino/vision_transformers.py inside get_ref_in, image_restoration_ref_model.py:215-247, whose only output is an arg-max).

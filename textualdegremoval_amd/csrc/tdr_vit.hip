@@ -796,6 +796,139 @@ __global__ __launch_bounds__(256) void select_window_kernel(const float* __restr
     for (long i = blockIdx.x * 256L + threadIdx.x; i < per; i += (long)gridDim.x * 256) out[(long)b * per + i] = src[i];
 }
 
+// ---- the window bank of matched tiled inference: the features of a ref's windows are computed once per image, every tile of that image
+// is matched against them.
+// resize_bilinear_kernel on windows n0 .. n0 + count - 1 of every image, read in place: the same expressions on the same values, the
+// plane pointer moved to the window's corner and the row pitch Wr -- the bits of resize_bilinear(unfold_windows(ref)) without the
+// [B*N][C][t][t] tensor.  dst [B*count][C][Hd][Wd], image-major.
+__global__ void window_resize_bilinear_kernel(const float* __restrict__ ref, int C, int Hr, int Wr, int t, int stride, int nx, int n0,
+                                              int count, float* __restrict__ dst, int Hd, int Wd, long planes) {
+    const int Hs = t, Ws = t;
+    const float sy = (float)Hs / (float)Hd, sx = (float)Ws / (float)Wd;
+    const long total = planes * Hd * Wd;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Wd);
+        const int y = (int)((i / Wd) % Hd);
+        const long pl = i / ((long)Wd * Hd);
+        const int c = (int)(pl % C);
+        const int n = n0 + (int)((pl / C) % count);
+        const long b = pl / C / count;
+        const float fy = fmaxf(((float)y + 0.5f) * sy - 0.5f, 0.f), fx = fmaxf(((float)x + 0.5f) * sx - 0.5f, 0.f);
+        const int y0 = min((int)fy, Hs - 1), x0 = min((int)fx, Ws - 1);
+        const int y1 = min(y0 + 1, Hs - 1), x1 = min(x0 + 1, Ws - 1);
+        const float ly = fy - (float)y0, lx = fx - (float)x0;
+        const float* p = ref + ((b * C + c) * Hr + (long)(n / nx) * stride) * Wr + (long)(n % nx) * stride;
+        const float top = p[y0 * Wr + x0] * (1.f - lx) + p[y0 * Wr + x1] * lx;
+        const float bot = p[y1 * Wr + x0] * (1.f - lx) + p[y1 * Wr + x1] * lx;
+        dst[i] = top * (1.f - ly) + bot * ly;
+    }
+}
+
+// token_corr_kernel with the roles turned round: one workgroup per (window of an image, band) reads its slice of the bank row ONCE
+// (float4 loads into LDS, BANK_CHUNK floats a round) and accumulates (dot, |L|^2) for every slot b with rows[b] == image and |R|^2
+// once for all of them, the slots' own rows coming from fl (a few MB per tile batch: L2).  Thread x takes the elements x, x + 256, ... of the band in ascending
+// order, masks the class-token and padding columns and reduces as token_corr_kernel does for its one pair -- per slot the same
+// additions in the same order, the same bits.  BANK_SLOTS slots a pass; more than that many tiles of one image in a batch take
+// another pass over the slice.  part [Bt][Nw][CORR_SPLIT][3].
+constexpr int BANK_SLOTS = 8;
+constexpr int BANK_CHUNK = 4096;
+__global__ __launch_bounds__(256) void token_corr_bank_kernel(const float* __restrict__ fl, const float* __restrict__ bank,
+                                                             const int* __restrict__ rows, int Bt, int D, int T1, int LD, int Nw,
+                                                             float* __restrict__ part) {
+    __shared__ __align__(16) float stage[BANK_CHUNK];
+    __shared__ float red[BANK_SLOTS][3][4];
+    __shared__ int slot[BANK_SLOTS], sng, snext;
+    const int w = blockIdx.x, img = blockIdx.y, sp = blockIdx.z;
+    const int nrows = (D + CORR_SPLIT - 1) / CORR_SPLIT, d0 = sp * nrows, d1 = min(D, d0 + nrows);
+    const long len = d1 > d0 ? (long)(d1 - d0) * LD : 0;          // (a band past D is empty: its partials are zeros, as there)
+    const long off = (long)d0 * LD;
+    const float* R = bank + ((long)img * Nw + w) * D * LD + off;
+    for (int b0 = 0; b0 < Bt;) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int ng = 0, b = b0;
+            for (; b < Bt && ng < BANK_SLOTS; ++b)
+                if (rows[b] == img) slot[ng++] = b;
+            sng = ng; snext = b;
+        }
+        __syncthreads();
+        const int ng = sng;
+        b0 = snext;
+        if (ng == 0) break;
+        const float* L[BANK_SLOTS];
+        // token_corr_kernel's three updates compile to fused multiply-adds; here they are spelled out -- c * c, shared by the slots,
+        // would otherwise be rounded on its own -- and |R|^2, the same for every slot of the image, is accumulated once
+        float dot[BANK_SLOTS], nl[BANK_SLOTS], nr = 0.f;
+#pragma unroll
+        for (int g = 0; g < BANK_SLOTS; ++g) {
+            L[g] = fl + (long)slot[min(g, ng - 1)] * D * LD + off;
+            dot[g] = nl[g] = 0.f;
+        }
+        for (long c0 = 0; c0 < len; c0 += BANK_CHUNK) {
+            const int m = (int)min((long)BANK_CHUNK, len - c0);       // a multiple of 4: LD is
+            __syncthreads();
+            for (int v = threadIdx.x * 4; v < m; v += 1024)
+                *reinterpret_cast<float4*>(&stage[v]) = *reinterpret_cast<const float4*>(&R[c0 + v]);
+            __syncthreads();
+            for (int j = threadIdx.x; j < m; j += 256) {
+                const long i = c0 + j;
+                const int col = (int)((off + i) % LD);
+                if (col == 0 || col >= T1) continue;         // class token column, padding
+                const float c = stage[j];
+                nr = fmaf(c, c, nr);
+#pragma unroll
+                for (int g = 0; g < BANK_SLOTS; ++g)
+                    if (g < ng) {
+                        const float a = L[g][i];
+                        dot[g] = fmaf(a, c, dot[g]);
+                        nl[g] = fmaf(a, a, nl[g]);
+                    }
+            }
+        }
+        const float s2 = wave_sum(nr);
+#pragma unroll
+        for (int g = 0; g < BANK_SLOTS; ++g)
+            if (g < ng) {
+                const float s0 = wave_sum(dot[g]), s1 = wave_sum(nl[g]);
+                if ((threadIdx.x & 63) == 0) { red[g][0][threadIdx.x >> 6] = s0; red[g][1][threadIdx.x >> 6] = s1; red[g][2][threadIdx.x >> 6] = s2; }
+            }
+        __syncthreads();
+        if (threadIdx.x < 3 * ng) {
+            const int g = threadIdx.x / 3, k = threadIdx.x % 3;
+            part[(((long)slot[g] * Nw + w) * CORR_SPLIT + sp) * 3 + k] = (red[g][k][0] + red[g][k][1]) + (red[g][k][2] + red[g][k][3]);
+        }
+    }
+}
+
+// select_window_kernel for the bank: first maximum of corr[b][.], then the chosen window of image rows[b] straight out of ref, rows of
+// t contiguous floats.  A slot whose row names no image gets index -1 and zeros; nothing outside ref is read.
+__global__ __launch_bounds__(256) void select_window_bank_kernel(const float* __restrict__ corr, const float* __restrict__ ref,
+                                                                const int* __restrict__ rows, int Nimg, int C, int Hr, int Wr, int t,
+                                                                int stride, int nx, int N, int* __restrict__ index,
+                                                                float* __restrict__ out) {
+    __shared__ int sbest;
+    const int b = blockIdx.y, img = rows[b];
+    const bool ok = img >= 0 && img < Nimg;
+    if (threadIdx.x == 0) {
+        int best = 0;
+        float bv = corr[(long)b * N];
+        for (int n = 1; n < N; ++n) {
+            const float v = corr[(long)b * N + n];
+            if (v > bv) { bv = v; best = n; }
+        }
+        sbest = best;
+        if (blockIdx.x == 0) index[b] = ok ? best : -1;
+    }
+    __syncthreads();
+    const long per = (long)C * t * t;
+    const float* src = ref + ((long)(ok ? img : 0) * C * Hr + (long)(sbest / nx) * stride) * Wr + (long)(sbest % nx) * stride;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < per; i += (long)gridDim.x * 256) {
+        const int x = (int)(i % t), y = (int)((i / t) % t);
+        const long c = i / ((long)t * t);
+        out[(long)b * per + i] = ok ? src[(c * Hr + y) * Wr + x] : 0.f;
+    }
+}
+
 inline int vgrid(long total, int cap = 16384) {
     long b = (total + 255) / 256;
     return (int)(b < cap ? (b < 1 ? 1 : b) : cap);
@@ -939,5 +1072,44 @@ extern "C" int tdr_token_match(const float* fl, const float* fr, const float* wi
     hipLaunchKernelGGL(token_corr_finish_kernel, dim3(tdr_cdiv(B * N, 64)), dim3(64), 0, st, ref_in, B * N, corr);
     hipLaunchKernelGGL(select_window_kernel, dim3(vgrid(per, 256), B), dim3(256), 0, st, corr, windows, N, (long)per, index, ref_in);
     TDR_LAUNCH_CHECK("token_match");
+    return TDR_OK;
+}
+
+extern "C" int tdr_window_resize_bilinear(const float* ref, int B, int C, int Hr, int Wr, int t, int stride, int n0, int count, float* dst,
+                                          int Hd, int Wd, void* stream) {
+    TDR_REQUIRE(ref && dst && B > 0 && C > 0 && t > 0 && t <= Hr && t <= Wr && stride > 0 && Hd > 0 && Wd > 0,
+                "tdr_window_resize_bilinear: bad argument");
+    const int ny = (Hr - t) / stride + 1, nx = (Wr - t) / stride + 1;
+    TDR_REQUIRE(n0 >= 0 && count > 0 && (long)n0 + count <= (long)ny * nx, "tdr_window_resize_bilinear: windows %d .. %d of %d", n0,
+                n0 + count - 1, ny * nx);
+    const long planes = (long)B * count * C, total = planes * Hd * Wd;
+    hipLaunchKernelGGL(window_resize_bilinear_kernel, dim3(vgrid(total)), dim3(256), 0, (hipStream_t)stream, ref, C, Hr, Wr, t, stride, nx,
+                       n0, count, dst, Hd, Wd, planes);
+    TDR_LAUNCH_CHECK("window_resize_bilinear");
+    return TDR_OK;
+}
+
+extern "C" int tdr_token_match_bank(const float* fl, const float* bank, const int* rows, const float* ref, int Bt, int Nimg, int Nw, int D,
+                                    int T1, int LD, int C, int Hr, int Wr, int t, int stride, int nx, float* ws, float* corr, int* index,
+                                    float* ref_in, void* stream) {
+    TDR_REQUIRE(fl && bank && rows && ref && ws && corr && index && ref_in, "tdr_token_match_bank: null pointer");
+    TDR_REQUIRE(Bt > 0 && Nimg > 0 && Nimg <= 65535 && Bt <= 65535 && D > 0 && C > 0 && t > 0 && t <= Hr && t <= Wr && stride > 0,
+                "tdr_token_match_bank: bad shape");
+    TDR_REQUIRE(LD % 4 == 0 && T1 <= LD, "tdr_token_match_bank: LD %d must be a multiple of 4 and >= T1 %d", LD, T1);
+    const int ny = (Hr - t) / stride + 1;
+    TDR_REQUIRE(nx == (Wr - t) / stride + 1 && Nw == ny * nx, "tdr_token_match_bank: %d windows, nx %d do not belong to a %d x %d ref", Nw,
+                nx, Hr, Wr);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t parts = (size_t)Bt * Nw * CORR_SPLIT * 3;
+    // (a slot whose row names no image is written by no workgroup: its partials stay zero, its corr 0)
+    if (hipMemsetAsync(ws, 0, parts * sizeof(float), st) != hipSuccess) {
+        tdr_set_error("tdr_token_match_bank: hipMemsetAsync failed");
+        return TDR_ERR_HIP;
+    }
+    hipLaunchKernelGGL(token_corr_bank_kernel, dim3(Nw, Nimg, CORR_SPLIT), dim3(256), 0, st, fl, bank, rows, Bt, D, T1, LD, Nw, ws);
+    hipLaunchKernelGGL(token_corr_finish_kernel, dim3(tdr_cdiv(Bt * Nw, 64)), dim3(64), 0, st, ws, Bt * Nw, corr);
+    hipLaunchKernelGGL(select_window_bank_kernel, dim3(vgrid((long)C * t * t, 256), Bt), dim3(256), 0, st, corr, ref, rows, Nimg, C, Hr, Wr,
+                       t, stride, nx, Nw, index, ref_in);
+    TDR_LAUNCH_CHECK("token_match_bank");
     return TDR_OK;
 }

@@ -197,6 +197,61 @@ class DinoMatcher:
         corr, index, ref_in = K.token_match(fl, fr, windows, N, T + 1)
         return ref_in, index, corr
 
+    @torch.no_grad()
+    def window_bank(self, ref, t, chunk=32):
+        """the tokens of every (t, t) window of every image of ref [N,3,Hr,Wr], computed once for all the tiles that will be matched
+        against them (match_bank): `chunk` windows per image at a time through kernels.window_resize -> tokens, so the resized windows
+        never exist all at once.  The tokens of an image do not depend on its batch-mates: the bits do not depend on `chunk`."""
+        if ref.dtype != torch.float32 or ref.dim() != 4:
+            raise TypeError('window_bank: ref must be a float32 [N,3,Hr,Wr] tensor')
+        ref = ref.contiguous()
+        N, _, Hr, Wr = ref.shape
+        ny, nx, stride = window_grid(Hr, Wr, t)
+        Nw, chunk = ny * nx, max(1, int(chunk))
+        Hd = int(math.ceil(t / self.patch) * self.patch)
+        feats = T = None
+        for n0 in range(0, Nw, chunk):
+            count = min(chunk, Nw - n0)
+            f, T = self.tokens(K.window_resize(ref, t, stride, n0, count, Hd, Hd), flat=FLAT)
+            if feats is None:
+                feats = torch.empty((N, Nw) + tuple(f.shape[1:]), dtype=torch.float32, device=ref.device)
+            feats[:, n0:n0 + count] = f.view((N, count) + tuple(f.shape[1:]))
+        return WindowBank(feats.view((N * Nw,) + tuple(feats.shape[2:])), ny, nx, stride, int(t), T)
+
+    @torch.no_grad()
+    def match_bank(self, tiles, bank, rows, ref):
+        """match() for a batch of tiles [Bt,3,t,t] against a bank of ref [N,3,Hr,Wr]: slot b against the windows of image rows[b]
+        (int32 [Bt] on the device) -> (ref_in [Bt,3,t,t], index [Bt] int32, corr [Bt,Nw]), the bits of match(tiles[b:b+1],
+        ref[rows[b]:rows[b]+1]); one ViT pass over the tiles only, no host synchronisation."""
+        t = bank.t
+        if tuple(tiles.shape[2:]) != (t, t):
+            raise ValueError(f'match_bank: tiles of {tuple(tiles.shape[2:])} against a bank of {t} x {t} windows')
+        Hd = int(math.ceil(t / self.patch) * self.patch)
+        fl, T = self.tokens(K.resize_bilinear(tiles.contiguous(), Hd, Hd), flat=FLAT)
+        assert T == bank.T
+        corr, index, ref_in = K.token_match_bank(fl, bank.feats, rows, ref.contiguous(), t, bank.stride, bank.nx, T + 1)
+        return ref_in, index, corr
+
+
+def window_grid(Hr, Wr, t):
+    """the (t, t) windows match() unfolds from a ref of Hr x Wr -> (ny, nx, stride): stride = int(t // 4), window w = wy * nx + wx at
+    (wy * stride, wx * stride)"""
+    Hr, Wr, t = int(Hr), int(Wr), int(t)
+    if t <= 0 or Hr < t or Wr < t:
+        raise ValueError(f'window_grid: a ref of {Hr} x {Wr} holds no window of {t} x {t}')
+    stride = int(t // 4)
+    if stride <= 0:
+        raise ValueError(f'window_grid: a window of {t} x {t} over a ref of {Hr} x {Wr} has stride 0')
+    return (Hr - t) // stride + 1, (Wr - t) // stride + 1, stride
+
+
+class WindowBank:
+    """what DinoMatcher.window_bank answers: feats [N * Nw, D, LD/32, 32] (image-major, window w = wy * nx + wx), the window grid
+    (ny, nx, stride) of window_grid, the window side t and the number of patch tokens T"""
+
+    def __init__(self, feats, ny, nx, stride, t, T):
+        self.feats, self.ny, self.nx, self.stride, self.t, self.T = feats, ny, nx, stride, t, T
+
 
 def random_vit_b14_state_dict(seed=0, embed=768, depth=12, grid=37, patch=14):
     """random-init ViT-B/14 state dict with the reference's key names (benchmarks only: no checkpoint is reachable

@@ -8,6 +8,7 @@ validation set.  A session packs the network's weights once and replays the forw
     sess.refresh()                 # the weights changed in place: re-pack (one launch), keep the graphs
     sess.release()                 # drop graphs, their pool, the packs
     out = sess.run_tiled(lq, ref, tile=256, overlap=32, tile_batch=4)      # an image of any size through the graph of ONE tile shape
+    out = sess.run_tiled(lq, ref, tile=256, matcher=dino_matcher)          # ... every tile against its DINOv2-matched window of ref
 
 The host-side bookkeeping (GraphLRU, session_key, what makes a session stale, the tile plan: tile_starts / tile_weights / tile_batches)
 needs no GPU and is tested without one."""
@@ -208,6 +209,7 @@ class InferenceSession:
         self.released = False
         self.captures = self.replays = self.rebuilds = 0
         self.tile_plans = OrderedDict()
+        self.last_match = None                   # what the matcher picked in the last run_tiled(..., matcher=) call
         self._build()
 
     # ---- weights
@@ -343,16 +345,31 @@ class InferenceSession:
             self.tile_plans.move_to_end(key)
         return plan
 
-    def _tiled(self, src, extra, tile, overlap, tile_batch, swap_rb):
+    def _tiled(self, src, extra, tile, overlap, tile_batch, swap_rb, matcher=None):
         self._alive()
         require_gpu(src, type(self.net).__name__)
         src = src.contiguous()
         N, H, W = (src.shape[0], src.shape[1], src.shape[2]) if src.dtype == torch.uint8 else (src.shape[0], src.shape[2], src.shape[3])
+        if matcher is not None:
+            ref = extra[0] if extra else None
+            if not torch.is_tensor(ref) or ref.dtype != torch.float32:
+                raise TypeError('run_tiled: with a matcher the first extra input is the ref, a float32 [N,3,Hr,Wr] tensor')
+            if ref.dim() != 4 or ref.shape[1] != 3:
+                raise ValueError(f'run_tiled: with a matcher the first extra input is the ref [N,3,Hr,Wr], not {tuple(ref.shape)}')
         for e in extra:
             if e is not None and e.shape[0] != N:
                 raise ValueError(f'run_tiled: an extra input of {e.shape[0]} rows for {N} images')
         plan = self._tile_plan(N, H, W, tile, overlap, tile_batch, src.device)
         B, held = plan.tile_batch, []
+        bank = picked = None
+        if matcher is not None:
+            from .dino import window_grid
+            if plan.th != plan.tw:
+                raise NotImplementedError(f'run_tiled: the matcher unfolds square windows; tiles of {plan.th} x {plan.tw} are not matched')
+            ref = ref.contiguous()
+            grid = window_grid(ref.shape[2], ref.shape[3], plan.th)
+            if tuple(ref.shape[2:]) != (plan.th, plan.tw):       # (else one window: top-1 of one candidate, the ref rows themselves)
+                bank, picked = matcher.window_bank(ref, plan.th), []      # once per call, for every tile of every image
 
         def take(out):
             full = full_size(out)
@@ -367,10 +384,23 @@ class InferenceSession:
         for k in range(len(plan.batches)):
             tiles = K.tile_gather(src, plan.table[k * B:(k + 1) * B], plan.th, plan.tw, swap_rb=swap_rb)
             rows = plan.image[k * B:(k + 1) * B]
-            self._run((tiles,) + tuple(e if e is None else e.index_select(0, rows) for e in extra), None, take)
+            others = tuple(e if e is None else e.index_select(0, rows) for e in (extra if bank is None else extra[1:]))
+            if bank is not None:
+                # the matcher runs eagerly in front of the replay: only the network's forward is captured, its key knows no ref size
+                ref_in, index, corr = matcher.match_bank(tiles, bank, rows, ref)
+                real = min(B, plan.n_tiles - k * B)
+                picked.append((index[:real], corr[:real]))
+                others = (ref_in,) + others
+            self._run((tiles,) + others, None, take)
+        if matcher is not None:
+            if bank is None:
+                index, corr = torch.zeros(plan.n_tiles, dtype=torch.int32, device=src.device), None
+            else:
+                index, corr = torch.cat([p[0] for p in picked]), torch.cat([p[1] for p in picked])
+            self.last_match = dict(index=index, corr=corr, grid=grid)
         return K.tile_blend(held[0], N, H, W, plan.ytabs, plan.xtabs)
 
-    def run_tiled(self, lq, *extra, tile=256, overlap=32, tile_batch=4):
+    def run_tiled(self, lq, *extra, tile=256, overlap=32, tile_batch=4, matcher=None):
         """lq float32 [N,C,H,W] of ANY size -> float32 [N,C_out,H,W], through forwards of one shape: the image is cut into tiles of `tile`
         (an int or (th, tw); min(tile, image) per dimension) that overlap by `overlap` pixels, the last tile of a row / column clamped
         to the border (tile_starts); the tiles of all N images run through the network in batches of exactly `tile_batch` (the last batch
@@ -389,18 +419,28 @@ class InferenceSession:
         contributes its full-size output, the last.  Scale-1 networks only (NotImplementedError otherwise).
 
         The device tables of a plan are kept per (N, H, W, th, tw, overlap, tile_batch) (the gather table holds the padding of the
-        last batch, hence tile_batch), at most TILE_PLANS of them: a repeated image size copies nothing to the device."""
+        last batch, hence tile_batch), at most TILE_PLANS of them: a repeated image size copies nothing to the device.
+
+        `matcher` (a dino.DinoMatcher): the first extra is the ref, float32 [N,3,Hr,Wr] of any size >= the tile, and every tile is
+        restored against the (t, t) window of its image's ref that `matcher.match(tile, ref[n])` picks -- what the train step pairs a
+        patch with -- instead of the whole ref.  The tokens of a ref's windows are computed once per call (matcher.window_bank), each
+        batch of tiles costs one ViT pass over the tiles and one pass over the bank (matcher.match_bank), run eagerly in front of the
+        replay: the captured forward sees (tile_batch, C, t, t) twice, ONE graph for every image size and every ref size.  Square
+        tiles only (NotImplementedError otherwise, as match()).  A ref of exactly (t, t) has one window: no ViT pass, the bits of the
+        call without a matcher.  Afterwards `sess.last_match` = dict(index int32 [n_tiles], corr float32 [n_tiles, Nw] (None in the
+        one-window case), grid (ny, nx, stride)): device tensors, image-major then row-major like the tiles, padding slots dropped."""
         if lq.dtype != torch.float32 or lq.dim() != 4:
             raise TypeError('run_tiled: lq must be a float32 [N,C,H,W] tensor')
-        return self._tiled(lq, extra, tile, overlap, tile_batch, False)
+        return self._tiled(lq, extra, tile, overlap, tile_batch, False, matcher)
 
-    def run_tiled_u8(self, lq_u8, extra=None, tile=256, overlap=32, tile_batch=4, bgr=True):
+    def run_tiled_u8(self, lq_u8, extra=None, tile=256, overlap=32, tile_batch=4, bgr=True, matcher=None):
         """run_tiled on bytes: lq_u8 uint8 [N,H,W,C] as cv2 decodes it -> uint8 [N,H,W,C].  The tiles are gathered straight from the bytes
         (converted as kernels.img_u8_to_planes converts, `bgr` exchanging channels 0 and 2 on the way in and back), the blended planes go
         through kernels.planes_to_img_u8: bit for bit planes_to_img_u8(run_tiled(img_u8_to_planes(lq_u8))), on the same graph.
-        `extra`: None, one tensor or a sequence; a uint8 one (a ref image [N,Hr,Wr,3]) is converted once per call, not once per tile."""
+        `extra`: None, one tensor or a sequence; a uint8 one (a ref image [N,Hr,Wr,3]) is converted once per call, not once per tile.
+        `matcher`: as in run_tiled, the (converted) first extra being the ref."""
         if lq_u8.dtype != torch.uint8 or lq_u8.dim() != 4:
             raise TypeError('run_tiled_u8: lq_u8 must be a uint8 [N,H,W,C] tensor')
         extra = () if extra is None else (extra,) if torch.is_tensor(extra) else tuple(extra)
         extra = tuple(K.img_u8_to_planes(e.contiguous(), swap_rb=bgr) if e is not None and e.dtype == torch.uint8 else e for e in extra)
-        return K.planes_to_img_u8(self._tiled(lq_u8, extra, tile, overlap, tile_batch, bool(bgr)), swap_rb=bgr)
+        return K.planes_to_img_u8(self._tiled(lq_u8, extra, tile, overlap, tile_batch, bool(bgr), matcher), swap_rb=bgr)

@@ -1679,6 +1679,38 @@ def token_match(fl, fr, windows, N, T1):
     return corr, index, ref_in
 
 
+def window_resize(ref, t, stride, n0, count, Hd, Wd):
+    """windows n0 ... n0 + count - 1 (unfold_windows' numbering) of every image of ref [B,C,Hr,Wr], resized bilinearly ->
+    [B * count, C, Hd, Wd], image-major: the bits of resize_bilinear(unfold_windows(ref, t, stride)) on those windows, read in place"""
+    B, Cc, Hr, Wr = ref.shape
+    assert ref.dtype == torch.float32 and ref.is_contiguous()
+    out = torch.empty(B * int(count), Cc, int(Hd), int(Wd), dtype=torch.float32, device=ref.device)
+    check(_lib.load().tdr_window_resize_bilinear(ref.data_ptr(), B, Cc, Hr, Wr, int(t), int(stride), int(n0), int(count), out.data_ptr(),
+                                                 int(Hd), int(Wd), _stream()), 'tdr_window_resize_bilinear')
+    return out
+
+
+def token_match_bank(fl, bank, rows, ref, t, stride, nx, T1):
+    """fl [Bt,D,LD/32,32] (the tiles' tokens), bank [Nimg*Nw,D,LD/32,32] (the tokens of every window of every ref image), rows int32 [Bt]
+    on the device (the image of each slot), ref [Nimg,C,Hr,Wr] -> (corr [Bt,Nw], index [Bt] int32, ref_in [Bt,C,t,t]): per slot
+    token_match against the windows of its image, the same bits; the chosen window is gathered from ref"""
+    Bt, D = fl.shape[0], fl.shape[1]
+    LD = fl.shape[2] * fl.shape[3]
+    Nimg, Cc, Hr, Wr = ref.shape
+    assert fl.is_contiguous() and bank.is_contiguous() and ref.is_contiguous() and ref.dtype == fl.dtype == bank.dtype == torch.float32
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.shape == (Bt,) and rows.device == fl.device
+    Nw = bank.shape[0] // Nimg
+    assert bank.shape[0] == Nimg * Nw and tuple(bank.shape[1:]) == tuple(fl.shape[1:]), (tuple(bank.shape), tuple(fl.shape), Nimg)
+    corr = torch.empty(Bt, Nw, dtype=torch.float32, device=fl.device)
+    index = torch.empty(Bt, dtype=torch.int32, device=fl.device)
+    ref_in = torch.empty(Bt, Cc, int(t), int(t), dtype=torch.float32, device=fl.device)
+    ws = workspace(Bt * Nw * 48 * 3, fl.device)
+    check(_lib.load().tdr_token_match_bank(fl.data_ptr(), bank.data_ptr(), rows.data_ptr(), ref.data_ptr(), Bt, Nimg, Nw, D, int(T1), LD, Cc,
+                                           Hr, Wr, int(t), int(stride), int(nx), ws.data_ptr(), corr.data_ptr(), index.data_ptr(),
+                                           ref_in.data_ptr(), _stream()), 'tdr_token_match_bank')
+    return corr, index, ref_in
+
+
 # ------------------------------------------------------------------ Restormer-ref (network_restormer_guided_arch.py)
 def dwgelu_fwd(t, w, b=None):
     """GDFN gate: gelu(dw(t)[:, :h]) * dw(t)[:, h:]"""

@@ -441,12 +441,20 @@ class RefGuidedImageCleanModel(BaseModel):
         net = self.net_g_ema if hasattr(self, 'net_g_ema') else self.net_g
         net.eval()
         val = self.opt.get('val') or {}
+        if val.get('tile_match') and not val.get('tile'):
+            raise ValueError('val.tile_match matches a reference window per tile: it needs val.tile (the tile size) as well')
         if val.get('tile'):
             # `val: {tile: 256, tile_overlap: 32, tile_batch: 4}`: every image, whatever its size, as overlapping tiles of the training
             # patch size through one captured graph (InferenceSession.run_tiled); implies the validation session
-            tile = val['tile']
+            # `tile_match: true`: every tile against the window of ref that the DINOv2 matcher picks for it, as the train step pairs them
+            tile, kw = val['tile'], {}
+            if val.get('tile_match'):
+                if self.net_ext is None:
+                    raise ValueError('ref is larger than lq: the DINOv2 window matcher needs path.pretrain_dino '
+                                     '(the reference loads it unconditionally, image_restoration_ref_model.py:83-86)')
+                kw['matcher'] = self.net_ext
             pred = self._val_session(net).run_tiled(img, self.ref, tile=tile if isinstance(tile, int) else tuple(tile),
-                                                    overlap=val.get('tile_overlap', 32), tile_batch=val.get('tile_batch', 4))
+                                                    overlap=val.get('tile_overlap', 32), tile_batch=val.get('tile_batch', 4), **kw)
         elif val.get('session', False):
             pred = self._val_session(net)(img, self.ref)
         else:
