@@ -25,7 +25,7 @@ extern "C" {
  * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local; still 112,
  * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8, then
  * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL, then tdr_tile_gather /
- * tdr_tile_blend, then tdr_window_resize_bilinear / tdr_token_match_bank -- no existing entry point
+ * tdr_tile_blend, then tdr_window_resize_bilinear / tdr_token_match_bank, then tdr_dihedral_gather / tdr_dihedral_mean -- no existing entry point
  * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there).
  * This header is the only written copy of the ABI: the binding (textualdegremoval_amd/_lib.py) derives its ctypes structs, argument lists and
  * version number from the text below at import and refuses a library whose tdr_version() differs.  Its parser knows the C this file uses and
@@ -457,6 +457,24 @@ int tdr_tile_gather(const void* src, int src_u8, int N, int C, int H, int W, int
                     float* out, void* stream);
 int tdr_tile_blend(const float* tiles, int N, int C, int H, int W, int th, int tw, int ny, int nx, const int* ystart, const int* yidx,
                    const float* yw, int Ky, const int* xstart, const int* xidx, const float* xw, int Kx, float* out, void* stream);
+/* Geometric self-ensemble (csrc/tdr_dihedral.hip; an addition to ABI 112): the network on the flips and transposes of an image, every answer
+ * transformed back and averaged -- `test_x8` of KAIR, `self_ensemble` of BasicSR; which forwards run is the caller's business, inference.py.
+ * Op codes 0 ... 7 over the last two dimensions: bit 0 the horizontal flip (x -> W-1-x), bit 1 the vertical flip (y -> H-1-y), bit 2 the
+ * transpose, applied after the flips; the inverse undoes them in the opposite order.  Ops 0 - 3 keep the shape (the straight class), ops
+ * 4 - 7 answer (W, H) (the transposed class).  A mask has bit `op` set for a selected op; members are stored op-major in ascending order.
+ *   tdr_dihedral_gather: out float32 [popcount(ops_mask)][N][C][Ho][Wo], out[k][n][c] = the bits of op_k applied to src[n][c].  src: float32
+ *     [N][C][H][W] (src_u8 = 0; swap_rb ignored), or uint8 [N][H][W][C], C in {1, 3, 6} (src_u8 = 1): converted as tdr_img_u8_to_planes
+ *     converts -- the same 256-entry table of float32(u) / 255.0f, channels 0 and 2 of a 3-channel image exchanged when swap_rb.  The
+ *     selected ops must be of one class (their outputs differ in shape); a mixed or an empty mask is refused.  One launch for all of them.
+ *   tdr_dihedral_mean: straight float32 [popcount(mask_s)][N][C][H][W], mask_s within 0x0f; transposed float32 [popcount(mask_t)][N][C][W][H],
+ *     mask_t within 0xf0; a null pointer goes with an empty mask, at least one op must be selected.  With the selected ops k0 < k1 < ...,
+ *     n of them: s = inv(m_k0); s = s + inv(m_k1); ...; v = s / float32(n) -- fp32 additions in ascending op order, no contraction, one
+ *     IEEE division.  Exactly one output: out_f32 [N][C][H][W] takes v; out_u8 [N][H][W][C] (C in {1, 3, 6}) takes
+ *     uint8(rint(min(max(v, 0), 1) * 255.0f)) with swap_rb -- the bits of tdr_planes_to_img_u8 on out_f32, without the float image in memory.
+ * The transposing ops pass through a 32 x 32 LDS tile, so reads and writes are both row-contiguous; no atomics, no device tables. */
+int tdr_dihedral_gather(const void* src, int src_u8, int N, int C, int H, int W, int swap_rb, int ops_mask, float* out, void* stream);
+int tdr_dihedral_mean(const float* straight, int mask_s, const float* transposed, int mask_t, int N, int C, int H, int W,
+                      float* out_f32, uint8_t* out_u8, int swap_rb, void* stream);
 
 /* TLSC local average pooling -- `AvgPool2d.forward` of models/archs/nafnet_local_arch.py:10-75 (fast_imp = False, auto_pad):
  * out[p][y][x] = mean of the k1' x k2' box (k' = min(size, k)) whose top-left corner is (clamp(y - (H - hv) / 2, 0, hv - 1),

@@ -9,9 +9,10 @@ validation set.  A session packs the network's weights once and replays the forw
     sess.release()                 # drop graphs, their pool, the packs
     out = sess.run_tiled(lq, ref, tile=256, overlap=32, tile_batch=4)      # an image of any size through the graph of ONE tile shape
     out = sess.run_tiled(lq, ref, tile=256, matcher=dino_matcher)          # ... every tile against its DINOv2-matched window of ref
+    out = sess.run_ensemble(lq, ref, ops=8)                                # geometric self-ensemble: flips / transposes in, their mean out
 
 The host-side bookkeeping (GraphLRU, session_key, what makes a session stale, the tile plan: tile_starts / tile_weights / tile_batches)
-needs no GPU and is tested without one."""
+and the definition of the self-ensemble (dihedral / dihedral_inverse / ensemble_ops) need no GPU and are tested without one."""
 from collections import OrderedDict
 
 import numpy as np
@@ -147,6 +148,67 @@ def tile_batches(n_tiles, tile_batch):
     return [idx[k:k + tile_batch] for k in range(0, len(idx), tile_batch)]
 
 
+# ---- the geometric self-ensemble of run_ensemble: the network on the 8 flips / transposes of an image, every answer transformed back, the
+# mean of them (`test_x8` of KAIR, `self_ensemble` of BasicSR).  These functions are the definition -- the kernels (csrc/tdr_dihedral.hip)
+# give their bits; they run on CPU tensors too.
+def dihedral(x, op):
+    """op code 0 ... 7 over the last two dimensions: bit 0 the horizontal flip (x -> W-1-x), bit 1 the vertical flip (y -> H-1-y), bit 2
+    the transpose, applied after the flips.  Ops 0 - 3 keep the shape (the straight class), ops 4 - 7 answer (..., W, H) (the transposed
+    class).  -> a view or a copy, not necessarily contiguous"""
+    if op & 1:
+        x = x.flip(-1)
+    if op & 2:
+        x = x.flip(-2)
+    if op & 4:
+        x = x.transpose(-2, -1)
+    return x
+
+
+def dihedral_inverse(y, op):
+    """undoes dihedral(., op): the transpose first, then the flips"""
+    if op & 4:
+        y = y.transpose(-2, -1)
+    if op & 2:
+        y = y.flip(-2)
+    if op & 1:
+        y = y.flip(-1)
+    return y
+
+
+def ensemble_ops(spec):
+    """which transforms a self-ensemble runs -> a sorted tuple of distinct op codes.  8 -> all of them, 4 -> the flips (0, 1, 2, 3), 2 ->
+    (0, 1), 1 -> (0,) (the plain forward); an iterable of op codes is de-duplicated and sorted.  ValueError for anything else."""
+    if isinstance(spec, (int, np.integer)) and not isinstance(spec, bool):
+        if int(spec) not in (1, 2, 4, 8):
+            raise ValueError(f'ensemble_ops: {spec} transforms -- 8 (flips and transposes), 4 (flips), 2 (horizontal flip), 1 '
+                             'or a list of op codes')
+        return tuple(range(int(spec)))
+    try:
+        ops = list(spec)
+    except TypeError:
+        raise ValueError(f'ensemble_ops: {spec!r} is neither 1, 2, 4, 8 nor an iterable of op codes') from None
+    if not ops or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 8 for k in ops):
+        raise ValueError(f'ensemble_ops: {spec!r} -- at least one op code, each an int in 0 ... 7')
+    return tuple(sorted({int(k) for k in ops}))
+
+
+def ensemble_classes(sel):
+    """the selected ops by the shape they answer -> ((straight ops, transposed=False), (transposing ops, True))"""
+    return (tuple(k for k in sel if k < 4), False), (tuple(k for k in sel if k >= 4), True)
+
+
+def ensemble_inputs(src, extra, ops, swap_rb):
+    """the inputs of one class's forward: the transforms `ops` of src and of every 4-D extra (the ref goes through the op its image goes
+    through), op-major; any other extra (k_v [N,10,1024]) repeated op-major"""
+    images = [K.dihedral_gather(src, ops, swap_rb=swap_rb)]
+    for e in extra:
+        if e is None or e.dim() != 4:
+            images.append(e if e is None else e.repeat(len(ops), *([1] * (e.dim() - 1))))
+        else:
+            images.append(K.dihedral_gather(e.contiguous(), ops, swap_rb=swap_rb))
+    return images
+
+
 class TilePlan:
     """the device tables of one (N, H, W, tile, overlap, tile_batch): a single int32 buffer (one host-to-device copy), cut into the
     gather table [T', 3] of (n, y0, x0) per padded tile slot, the image index [T'] of every slot, and per dimension start [n], idx [L, 2]
@@ -193,7 +255,10 @@ class InferenceSession:
     shape.
 
     run_tiled / run_tiled_u8 cut images of any size into overlapping tiles of one size, run the tiles through the forward in batches of
-    one size -- one key, one graph, whatever sizes follow -- and blend the tile outputs (see run_tiled)."""
+    one size -- one key, one graph, whatever sizes follow -- and blend the tile outputs (see run_tiled).
+
+    run_ensemble / run_ensemble_u8 (and `ensemble=` of the tiled calls) run the geometric self-ensemble: two small launches around
+    forwards that go through the same ladder (see run_ensemble)."""
 
     TILE_PLANS = 32                              # device tables kept for repeated (N, H, W, tile, overlap, tile_batch)
 
@@ -331,6 +396,72 @@ class InferenceSession:
             raise TypeError('run_u8: lq_u8 must be a uint8 [N,H,W,C] tensor')
         return self._run(images, ('u8', bool(bgr)))
 
+    # ---- self-ensemble
+    def _ensemble(self, src, extra, ops, swap_rb, u8, forward):
+        """`forward(images, transposed)` -> the float32 outputs [k * N, C_out, Ho, Wo] of one class's stack, a tensor the next forward
+        does not overwrite"""
+        self._alive()
+        sel = ensemble_ops(ops)
+        require_gpu(src, type(self.net).__name__)
+        src = src.contiguous()
+        N, (H, W) = src.shape[0], (src.shape[1:3] if src.dtype == torch.uint8 else src.shape[2:])
+        outs = []
+        for cls, transposed in ensemble_classes(sel):
+            out = forward(ensemble_inputs(src, extra, cls, swap_rb), transposed) if cls else None
+            want = (len(cls) * N, (W, H) if transposed else (H, W))
+            if out is not None and (out.dim() != 4 or (out.shape[0], tuple(out.shape[2:])) != want):
+                raise NotImplementedError(f'self-ensemble: {type(self.net).__name__} answers {tuple(out.shape)} to {want[0]} images of '
+                                          f'{want[1][0]} x {want[1][1]}; only networks of scale 1 are averaged')
+            outs.append(out)
+        return K.dihedral_mean(outs[0], outs[1], sel, N, u8=u8, swap_rb=swap_rb)
+
+    def _ensemble_forward(self, images, transposed):
+        # (a copy: the other class may replay the same graph and overwrite its static output)
+        return self._run(tuple(images), None, lambda out: full_size(out).clone(memory_format=torch.contiguous_format))
+
+    def run_ensemble(self, lq, *extra, ops=8):
+        """geometric self-ensemble: lq float32 [N,C,H,W] -> float32 [N,C_out,H,W], the mean over the selected transforms of
+        dihedral_inverse(net(dihedral(lq, op), ...), op) (`test_x8` of KAIR, `self_ensemble` of BasicSR).  `ops`: 8 (flips and transposes),
+        4 (flips), 2 (horizontal flip), 1, or an iterable of op codes (ensemble_ops).
+
+        The selected ops fall into two classes by the shape they give: straight (0 - 3: [.., H, W]) and transposed (4 - 7: [.., W, H]).
+        Per class ONE launch (kernels.dihedral_gather) stacks the transforms of lq op-major -- and of every 4-D extra: the ref goes through
+        the op its image goes through (MASA's geometry is symmetric under transposition, a transposed pair is valid whenever the original
+        is); any other extra (k_v [N,10,1024]) is repeated op-major -- and ONE forward of len(class ops) * N images runs through the
+        same pack plan and warm / capture / replay ladder as `sess(...)`, key (k * N, C, Ho, Wo): two keys, one for a square image whose
+        classes hold equally many ops.  One more launch (kernels.dihedral_mean) transforms every answer back, adds them in ascending op
+        order in fp32 and divides by their number.  A list-valued forward (SFNet) contributes its full-size output, the last.
+
+        The limits of the network hold as they are, for the stacked batch and for the transposed shape (the 16 images of
+        NAFNetDynamicFusion, width multiples): its error comes through.  ops=1 gives the bits of sess(lq, *extra).
+
+        THE RESULT DEPENDS ON THE BATCH COMPOSITION as far as a sample's bits depend on its batch-mates: it is defined through the stacked
+        forwards, not through eight separate ones."""
+        if lq.dtype != torch.float32 or lq.dim() != 4:
+            raise TypeError('run_ensemble: lq must be a float32 [N,C,H,W] tensor')
+        return self._ensemble(lq, extra, ops, False, False, self._ensemble_forward)
+
+    def run_ensemble_u8(self, lq_u8, ref_u8=None, bgr=True, ops=8):
+        """run_ensemble on bytes: lq_u8 / ref_u8 uint8 [N,H,W,C] as cv2 decodes them -> uint8 [N,H,W,C].  The transforms are gathered
+        straight from the bytes (converted as kernels.img_u8_to_planes converts, `bgr` exchanging channels 0 and 2 on the way in and back)
+        and the mean writes the bytes itself, no float image in between: bit for bit
+        planes_to_img_u8(run_ensemble(img_u8_to_planes(lq_u8), ...)), on the float call's keys and graphs -- the gather and the mean run
+        eagerly around the replay, as in the tiled calls.  A second input that is not uint8 is passed on as in run_u8."""
+        if lq_u8.dtype != torch.uint8 or lq_u8.dim() != 4:
+            raise TypeError('run_ensemble_u8: lq_u8 must be a uint8 [N,H,W,C] tensor')
+        return self._ensemble(lq_u8, () if ref_u8 is None else (ref_u8,), ops, bool(bgr), True, self._ensemble_forward)
+
+    def _tiled_ensemble(self, src, extra, tile, overlap, tile_batch, swap_rb, u8, ops, matcher):
+        if matcher is not None:
+            raise NotImplementedError('run_tiled: a matcher together with ensemble= is not implemented (the matched window of a transformed '
+                                      'tile is not the transformed window)')
+        th, tw = (tile, tile) if isinstance(tile, int) else tile
+
+        def forward(images, transposed):
+            return self._tiled(images[0], tuple(images[1:]), (tw, th) if transposed else (th, tw), overlap, tile_batch, False)
+
+        return self._ensemble(src, extra, ops, swap_rb, u8, forward)
+
     # ---- tiled
     def _tile_plan(self, N, H, W, tile, overlap, tile_batch, device):
         th, tw = (tile, tile) if isinstance(tile, int) else tile
@@ -400,7 +531,7 @@ class InferenceSession:
             self.last_match = dict(index=index, corr=corr, grid=grid)
         return K.tile_blend(held[0], N, H, W, plan.ytabs, plan.xtabs)
 
-    def run_tiled(self, lq, *extra, tile=256, overlap=32, tile_batch=4, matcher=None):
+    def run_tiled(self, lq, *extra, tile=256, overlap=32, tile_batch=4, matcher=None, ensemble=None):
         """lq float32 [N,C,H,W] of ANY size -> float32 [N,C_out,H,W], through forwards of one shape: the image is cut into tiles of `tile`
         (an int or (th, tw); min(tile, image) per dimension) that overlap by `overlap` pixels, the last tile of a row / column clamped
         to the border (tile_starts); the tiles of all N images run through the network in batches of exactly `tile_batch` (the last batch
@@ -428,19 +559,29 @@ class InferenceSession:
         replay: the captured forward sees (tile_batch, C, t, t) twice, ONE graph for every image size and every ref size.  Square
         tiles only (NotImplementedError otherwise, as match()).  A ref of exactly (t, t) has one window: no ViT pass, the bits of the
         call without a matcher.  Afterwards `sess.last_match` = dict(index int32 [n_tiles], corr float32 [n_tiles, Nw] (None in the
-        one-window case), grid (ny, nx, stride)): device tensors, image-major then row-major like the tiles, padding slots dropped."""
+        one-window case), grid (ny, nx, stride)): device tensors, image-major then row-major like the tiles, padding slots dropped.
+
+        `ensemble` (None, or what run_ensemble's `ops` takes): the self-ensemble of the tiled run -- by definition kernels.dihedral_mean
+        over the two classes of run_tiled(the dihedral-gathered stack of len(class ops) * N images, the extras transformed as in
+        run_ensemble, tile=(th, tw) -- (tw, th) for the transposed class), same overlap and tile_batch.  With square tiles one graph still
+        serves every image size.  Not together with a matcher (NotImplementedError)."""
         if lq.dtype != torch.float32 or lq.dim() != 4:
             raise TypeError('run_tiled: lq must be a float32 [N,C,H,W] tensor')
+        if ensemble is not None:
+            return self._tiled_ensemble(lq, extra, tile, overlap, tile_batch, False, False, ensemble, matcher)
         return self._tiled(lq, extra, tile, overlap, tile_batch, False, matcher)
 
-    def run_tiled_u8(self, lq_u8, extra=None, tile=256, overlap=32, tile_batch=4, bgr=True, matcher=None):
+    def run_tiled_u8(self, lq_u8, extra=None, tile=256, overlap=32, tile_batch=4, bgr=True, matcher=None, ensemble=None):
         """run_tiled on bytes: lq_u8 uint8 [N,H,W,C] as cv2 decodes it -> uint8 [N,H,W,C].  The tiles are gathered straight from the bytes
         (converted as kernels.img_u8_to_planes converts, `bgr` exchanging channels 0 and 2 on the way in and back), the blended planes go
         through kernels.planes_to_img_u8: bit for bit planes_to_img_u8(run_tiled(img_u8_to_planes(lq_u8))), on the same graph.
         `extra`: None, one tensor or a sequence; a uint8 one (a ref image [N,Hr,Wr,3]) is converted once per call, not once per tile.
-        `matcher`: as in run_tiled, the (converted) first extra being the ref."""
+        `matcher`: as in run_tiled, the (converted) first extra being the ref.  `ensemble`: as in run_tiled; the transforms are gathered
+        from the bytes and the mean writes the bytes (kernels.dihedral_mean(u8=True))."""
         if lq_u8.dtype != torch.uint8 or lq_u8.dim() != 4:
             raise TypeError('run_tiled_u8: lq_u8 must be a uint8 [N,H,W,C] tensor')
         extra = () if extra is None else (extra,) if torch.is_tensor(extra) else tuple(extra)
         extra = tuple(K.img_u8_to_planes(e.contiguous(), swap_rb=bgr) if e is not None and e.dtype == torch.uint8 else e for e in extra)
+        if ensemble is not None:
+            return self._tiled_ensemble(lq_u8, extra, tile, overlap, tile_batch, bool(bgr), True, ensemble, matcher)
         return K.planes_to_img_u8(self._tiled(lq_u8, extra, tile, overlap, tile_batch, bool(bgr), matcher), swap_rb=bgr)

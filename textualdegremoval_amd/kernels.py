@@ -1346,6 +1346,52 @@ def tile_blend(tiles, N, H, W, ytabs, xtabs):
     return out
 
 
+def _ops_mask(ops):
+    mask = 0
+    for op in ops:
+        if not 0 <= int(op) < 8:
+            raise ValueError(f'dihedral op {op!r}: the op codes are 0 ... 7')
+        mask |= 1 << int(op)
+    return mask
+
+
+def dihedral_gather(src, ops, swap_rb=True):
+    """the transforms `ops` (op codes of inference.dihedral, all of one class: 0 - 3 or 4 - 7) of every image: src float32 [N,C,H,W] or
+    uint8 [N,H,W,C] (C in {1, 3, 6}; converted as img_u8_to_planes converts, `swap_rb` included -- ignored for a float source) ->
+    float32 [len(ops) * N, C, Ho, Wo], op-major in ascending op order, (Ho, Wo) = (W, H) for the transposing class; one launch
+    (csrc/tdr_dihedral.hip)"""
+    u8 = src.dtype == torch.uint8
+    assert (u8 or src.dtype == torch.float32) and src.dim() == 4 and src.is_contiguous()
+    N, Cc, H, W = (src.shape[0], src.shape[3], src.shape[1], src.shape[2]) if u8 else src.shape
+    mask = _ops_mask(ops)
+    Ho, Wo = (W, H) if mask & 0xf0 else (H, W)
+    out = torch.empty(bin(mask).count('1') * N, Cc, Ho, Wo, dtype=torch.float32, device=src.device)
+    check(_lib.load().tdr_dihedral_gather(src.data_ptr(), int(u8), N, Cc, H, W, int(bool(swap_rb)), mask, _p(out), _stream()),
+          'tdr_dihedral_gather')
+    return out
+
+
+def dihedral_mean(straight, transposed, ops, N, u8=False, swap_rb=True):
+    """the self-ensemble's average: straight float32 [ks * N, C, H, W], the members of the selected ops below 4 (op-major, ascending; None
+    without one), transposed float32 [kt * N, C, W, H], those of the ops from 4 -> float32 [N,C,H,W]: every member transformed back
+    (inference.dihedral_inverse), added in ascending op order in fp32, divided by len(ops); with `u8` uint8 [N,H,W,C] instead, the bits
+    of planes_to_img_u8(that, swap_rb=swap_rb) -- one launch either way (csrc/tdr_dihedral.hip)"""
+    mask = _ops_mask(ops)
+    some = straight if straight is not None else transposed
+    if some is None:
+        raise ValueError('dihedral_mean: no members')
+    for t, k in ((straight, bin(mask & 0x0f).count('1')), (transposed, bin(mask & 0xf0).count('1'))):
+        assert t is None or (t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous() and t.shape[0] == k * N), (k, N)
+    Cc = some.shape[1]
+    H, W = some.shape[2:] if straight is not None else (some.shape[3], some.shape[2])
+    if straight is not None and transposed is not None:
+        assert tuple(transposed.shape[1:]) == (Cc, W, H), (tuple(straight.shape), tuple(transposed.shape))
+    out = torch.empty((N, H, W, Cc) if u8 else (N, Cc, H, W), dtype=torch.uint8 if u8 else torch.float32, device=some.device)
+    check(_lib.load().tdr_dihedral_mean(_p(straight), mask & 0x0f, _p(transposed), mask & 0xf0, N, Cc, H, W, 0 if u8 else out.data_ptr(),
+                                        out.data_ptr() if u8 else 0, int(bool(swap_rb)), _stream()), 'tdr_dihedral_mean')
+    return out
+
+
 def relu_bwd(go, act):
     assert go.is_contiguous() and act.is_contiguous()
     out = torch.empty_like(go)

@@ -443,6 +443,9 @@ class RefGuidedImageCleanModel(BaseModel):
         val = self.opt.get('val') or {}
         if val.get('tile_match') and not val.get('tile'):
             raise ValueError('val.tile_match matches a reference window per tile: it needs val.tile (the tile size) as well')
+        if val.get('ensemble') and val.get('tile_match'):
+            raise ValueError('val.ensemble together with val.tile_match is not implemented (InferenceSession.run_tiled refuses a matcher '
+                             'with ensemble=)')
         if val.get('tile'):
             # `val: {tile: 256, tile_overlap: 32, tile_batch: 4}`: every image, whatever its size, as overlapping tiles of the training
             # patch size through one captured graph (InferenceSession.run_tiled); implies the validation session
@@ -453,8 +456,14 @@ class RefGuidedImageCleanModel(BaseModel):
                     raise ValueError('ref is larger than lq: the DINOv2 window matcher needs path.pretrain_dino '
                                      '(the reference loads it unconditionally, image_restoration_ref_model.py:83-86)')
                 kw['matcher'] = self.net_ext
+            if val.get('ensemble'):
+                # `ensemble: 8`: the geometric self-ensemble of the tiled run (flips and transposes in, their mean out)
+                kw['ensemble'] = val['ensemble']
             pred = self._val_session(net).run_tiled(img, self.ref, tile=tile if isinstance(tile, int) else tuple(tile),
                                                     overlap=val.get('tile_overlap', 32), tile_batch=val.get('tile_batch', 4), **kw)
+        elif val.get('ensemble'):
+            # `val: {ensemble: 8}` without tiles: InferenceSession.run_ensemble; implies the validation session
+            pred = self._val_session(net).run_ensemble(img, self.ref, ops=val['ensemble'])
         elif val.get('session', False):
             pred = self._val_session(net)(img, self.ref)
         else:
