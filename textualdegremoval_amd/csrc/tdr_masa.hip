@@ -456,7 +456,10 @@ __global__ __launch_bounds__(256) void transfer_bwd_kernel(const float* __restri
     }
     float da = 0.f;
     const int c0 = blockIdx.y * cpb, c1 = min(c0 + cpb, C);
-    const float fscale = FIXED ? ldexpf(1.f, fixed_shift(amax_bits[0])) : 1.f;
+    // the shift passes 127 once max|dout| < 2^-82 (2^shift is no float then): the value itself is scaled, not multiplied by a
+    // scale.  An absmax word of 0 means dout == 0 everywhere: nothing to scatter.
+    const int shift = FIXED ? fixed_shift(amax_bits[0]) : 0;
+    const bool scatter = !FIXED || amax_bits[0] != 0u;
     for (int c = c0; c < c1; ++c) {
         const float* f = feat + ((long)n * C + c) * HWf;
         const float go = dout[(long)n * dout_ns + (long)c * HWo + pix];
@@ -466,7 +469,8 @@ __global__ __launch_bounds__(256) void transfer_bwd_kernel(const float* __restri
         for (int k = 0; k < 9; ++k)
             if (mult[k] > 0.f) {
                 acc += mult[k] * f[g.src[k]];
-                if (FIXED) atomicAdd(&dfacc[((long)n * C + c) * HWf + g.src[k]], (unsigned long long)__float2ll_rn(gv * mult[k] * fscale));   // two's complement
+                if (!scatter) continue;
+                if (FIXED) atomicAdd(&dfacc[((long)n * C + c) * HWf + g.src[k]], (unsigned long long)__float2ll_rn(ldexpf(gv * mult[k], shift)));   // two's complement
                 else atomicAdd(&dfeat[((long)n * C + c) * HWf + g.src[k]], gv * mult[k]);
             }
         da += go * acc * g.inv_cnt;
