@@ -25,7 +25,8 @@ extern "C" {
  * text-embedding modulation of NAFNetDynamicFusion, tdr_kvproj_* / tdr_modln_fwd / tdr_nc_affine* / tdr_modgate_*; 109: tdr_niqe_*; 110: tdr_wgrad3x3_p16_group*; 111: tdr_dyn_*_infer; 112: tdr_naf_tail_infer_local; still 112,
  * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8, then
  * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL, then tdr_tile_gather /
- * tdr_tile_blend, then tdr_window_resize_bilinear / tdr_token_match_bank, then tdr_dihedral_gather / tdr_dihedral_mean -- no existing entry point
+ * tdr_tile_blend, then tdr_window_resize_bilinear / tdr_token_match_bank, then tdr_dihedral_gather / tdr_dihedral_mean, then
+ * tdr_val_metrics_ws_bytes / tdr_val_metrics -- no existing entry point
  * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there).
  * This header is the only written copy of the ABI: the binding (textualdegremoval_amd/_lib.py) derives its ctypes structs, argument lists and
  * version number from the text below at import and refuses a library whose tdr_version() differs.  Its parser knows the C this file uses and
@@ -411,6 +412,32 @@ int tdr_ssim3d(const float* img1, const float* img2, int H, int W, int C, float 
  * doubles; out: 1 double = mean of the SSIM map.  Filtering, the SSIM map and its mean are evaluated in double. */
 int64_t tdr_ssim_y64_ws_doubles(int H, int W);
 int tdr_ssim_y64(const float* img1, const float* img2, int H, int W, double* ws, double* out, void* stream);
+
+/* Validation metrics without the host trip (csrc/tdr_valmetrics.hip; an addition to ABI 112): what `use_image: true` validation computes per
+ * image -- tensor2img, then calculate_psnr / calculate_ssim of metrics/psnr_ssim.py -- from device tensors, for all N images in one call.
+ * Each of pred and gt is EITHER float32 planes [N][C][.][.] (`pred`, with the image / channel / row strides in elements: a slice of a padded
+ * buffer needs no copy) OR dense uint8 [N][H][W][C] (`pred_u8`; the strides are ignored); the other pointer is NULL; the two may differ in
+ * form.  C is 1 or 3.  A float source is quantised as tdr_planes_to_img_u8 quantises: uint8(rint(min(max(v, 0), 1) * 255.0f)), float32
+ * product, ties to even, and swap_rb exchanges channels 0 and 2 of a 3-channel FLOAT source (tensor2img(rgb2bgr=)); bytes are taken as they
+ * are.  Finite inputs only.  Everything below is defined on these bytes, on the (H - 2 crop) x (W - 2 crop) region left after `crop` pixels
+ * are removed on every side (2 crop < H, W).
+ * what_mask selects (an empty mask is refused): 1 PSNR, 2 SSIM, 4 PSNR-Y, 8 SSIM-Y, 16 the Y planes alone (needs y_pred or y_gt).
+ * out: double [N][8], written whole:
+ *   [0] S = sum (a - b)^2 over the bytes, an exact integer (S < 2^53); [1] the largest byte of pred; [2] the element count
+ *       -- calculate_psnr is 20 log10(max_value / sqrt(S / count)) with max_value = 1 if [1] <= 1 else 255, the caller's to finish;
+ *   [3] (mask 2) the float tdr_ssim3d returns for the two cropped [h][w][C] byte images with that max_value rule applied per image
+ *       -- the same bits: tiles counted from the crop origin, one arithmetic for both (csrc/tdr_ssim_core.h);
+ *   [4] (mask 4, or a Y plane asked for) sum (ya - yb)^2 over the Y planes, differences and sum in double, fixed order; [5] its count;
+ *   [6] (mask 8) the double tdr_ssim_y64 returns for the two Y planes, the same bits;  [7] 0.  Unselected entries are 0.
+ * The Y plane is metrics/metric_util.py:34-47 (to_y_channel) on the bytes: f = float32(u) / 255 (the 256-entry table), C = 3:
+ * y = float32(((double(f0) * 24.966 + double(f1) * 128.553) + double(f2) * 65.481 + 16.0) / 255.0) * 255.0f, unfused double products and
+ * sums in that order, f0 ... f2 the channels after swap_rb (the coefficients go by position); C = 1: y = f * 255.0f.  y_pred / y_gt: float32
+ * [N][H - 2 crop][W - 2 crop], each may be NULL, receive the planes.  ws: tdr_val_metrics_ws_bytes(N, H, W) bytes (16-byte aligned; enough
+ * for any crop and either C).  Five launches at most, no atomics, no host synchronisation: the same call returns the same bits. */
+int64_t tdr_val_metrics_ws_bytes(int N, int H, int W);
+int tdr_val_metrics(const float* pred, const uint8_t* pred_u8, int64_t pred_ns, int64_t pred_cs, int64_t pred_rs, const float* gt,
+                    const uint8_t* gt_u8, int64_t gt_ns, int64_t gt_cs, int64_t gt_rs, int N, int C, int H, int W, int crop, int swap_rb,
+                    int what_mask, float* y_pred, float* y_gt, void* ws, double* out, void* stream);
 
 /* The block features of the no-reference NIQE metric -- metrics/niqe.py:10-139 (estimate_aggd_param, compute_feature and the two-scale
  * loop of niqe; the 36 x 36 Gaussian-model tail of :140-155 is the caller's, on the host).  y [H][W] float32: the gray / Y image in

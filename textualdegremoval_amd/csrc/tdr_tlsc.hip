@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "tdr_common.h"
+#include "tdr_ssim_core.h"
 #include "../../include/tdr.h"
 
 namespace {
@@ -61,60 +62,23 @@ __global__ __launch_bounds__(256) void tlsc_hmean_kernel(const float* __restrict
     }
 }
 
-// ---- float64 SSIM of one channel (BORDER_REPLICATE): a workgroup owns a 16 x 16 tile, stages the 26 x 26 haloed tile of both images
-// as doubles, filters the five fields separably (cv2.filter2D applies the outer product window; separable evaluation differs from it
-// only by double rounding), and writes one partial sum.
-constexpr int ST = 16, SR = 5, SE = ST + 2 * SR;
-struct SsimYArgs { const float* a; const float* b; int H, W; double c1, c2; double g[11]; double* partial; };
+// ---- float64 SSIM of one channel (BORDER_REPLICATE): the workgroup body lives in tdr_ssim_core.h (tdr_valmetrics.hip runs the same arithmetic
+// on Y planes formed from the quantised bytes of a cropped image)
+struct SsimYArgs { const float* a; const float* b; tdr_ssim::SsimYParams q; double* partial; };
+
+struct PlaneLoader {
+    const float* pa; const float* pb; int W;
+    __device__ __forceinline__ float a(int y, int x) const { return pa[(long)y * W + x]; }
+    __device__ __forceinline__ float b(int y, int x) const { return pb[(long)y * W + x]; }
+};
 
 __global__ __launch_bounds__(256) void ssim_y64_kernel(SsimYArgs p) {
-    __shared__ double s0[5][SE][SE + 1];
-    __shared__ double s1[5][SE][ST + 1];
-    __shared__ double red[4];
-    const int tid = threadIdx.x, x0 = blockIdx.x * ST, y0 = blockIdx.y * ST;
-    for (int i = tid; i < SE * SE; i += 256) {
-        const int r = i / SE, c = i - r * SE;
-        const int gy = min(max(y0 + r - SR, 0), p.H - 1), gx = min(max(x0 + c - SR, 0), p.W - 1);
-        const double a = (double)p.a[(long)gy * p.W + gx], b = (double)p.b[(long)gy * p.W + gx];
-        s0[0][r][c] = a; s0[1][r][c] = b; s0[2][r][c] = a * a; s0[3][r][c] = b * b; s0[4][r][c] = a * b;
-    }
-    __syncthreads();
-    for (int i = tid; i < 5 * SE * ST; i += 256) {          // along W
-        const int f = i / (SE * ST), rem = i - f * (SE * ST), r = rem / ST, c = rem - r * ST;
-        double v = 0.0;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) v += p.g[k] * s0[f][r][c + k];
-        s1[f][r][c] = v;
-    }
-    __syncthreads();
-    const int ty = tid >> 4, tx = tid & 15;
-    double m[5];
-#pragma unroll
-    for (int f = 0; f < 5; ++f) {
-        double v = 0.0;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) v += p.g[k] * s1[f][ty + k][tx];
-        m[f] = v;
-    }
-    double val = 0.0;
-    if (y0 + ty < p.H && x0 + tx < p.W) {
-        const double mu1 = m[0], mu2 = m[1];
-        const double s11 = m[2] - mu1 * mu1, s22 = m[3] - mu2 * mu2, s12 = m[4] - mu1 * mu2;
-        val = ((2 * mu1 * mu2 + p.c1) * (2 * s12 + p.c2)) / ((mu1 * mu1 + mu2 * mu2 + p.c1) * (s11 + s22 + p.c2));
-    }
-    // fixed-order block reduction
-    for (int o = 32; o > 0; o >>= 1) val += __shfl_xor(val, o, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = val;
-    __syncthreads();
-    if (tid == 0) p.partial[blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    const PlaneLoader ld{p.a, p.b, p.q.W};
+    tdr_ssim::ssim_y64_tile(p.q, ld, p.partial);
 }
 
 __global__ void ssim_y64_finish_kernel(const double* __restrict__ partial, int n, double inv, double* __restrict__ out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        double s = 0.0;
-        for (int i = 0; i < n; ++i) s += partial[i];
-        out[0] = s * inv;
-    }
+    if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = tdr_ssim::ssim_y64_fold(partial, n, inv);
 }
 
 }  // namespace
@@ -147,11 +111,8 @@ extern "C" int64_t tdr_ssim_y64_ws_doubles(int H, int W) { return (int64_t)tdr_c
 extern "C" int tdr_ssim_y64(const float* img1, const float* img2, int H, int W, double* ws, double* out, void* stream) {
     TDR_REQUIRE(img1 && img2 && ws && out && H > 0 && W > 0, "tdr_ssim_y64: bad argument");
     SsimYArgs p;
-    p.a = img1; p.b = img2; p.H = H; p.W = W;
-    p.c1 = (0.01 * 255) * (0.01 * 255); p.c2 = (0.03 * 255) * (0.03 * 255);
-    double sum = 0.0;                                 // cv2.getGaussianKernel(11, 1.5): exp(-(i - 5)^2 / (2 sigma^2)), normalised
-    for (int i = 0; i < 11; ++i) { p.g[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); sum += p.g[i]; }
-    for (int i = 0; i < 11; ++i) p.g[i] /= sum;
+    p.a = img1; p.b = img2;
+    tdr_ssim::ssim_y64_fill(p.q, H, W);
     p.partial = ws;
     const dim3 grid(tdr_cdiv(W, 16), tdr_cdiv(H, 16));
     hipStream_t st = (hipStream_t)stream;

@@ -2195,6 +2195,57 @@ def ssim_y64(img1, img2):
     return float(out.item())
 
 
+# what_mask of tdr_val_metrics and the columns of its rows (include/tdr.h)
+VALM_PSNR, VALM_SSIM, VALM_PSNR_Y, VALM_SSIM_Y, VALM_Y_PLANES = 1, 2, 4, 8, 16
+VALM_WHAT = {'psnr': VALM_PSNR, 'ssim': VALM_SSIM, 'psnr_y': VALM_PSNR_Y, 'ssim_y': VALM_SSIM_Y, 'y': VALM_Y_PLANES}
+VALM_S, VALM_MAX, VALM_COUNT, VALM_SSIM3D, VALM_SY, VALM_COUNT_Y, VALM_SSIMY = 0, 1, 2, 3, 4, 5, 6
+
+
+def _valm_source(t, name):
+    """-> (float pointer, byte pointer, image / channel / row strides, (N, C, H, W)) of one val_metrics operand"""
+    if t.dim() != 4 or not t.is_cuda:
+        raise ValueError(f'val_metrics: {name} must be a 4-D device tensor, float32 [N,C,H,W] or uint8 [N,H,W,C]')
+    if t.dtype == torch.uint8:
+        t = t if t.is_contiguous() else t.contiguous()
+        N, H, W, Cc = t.shape
+        return t, 0, t.data_ptr(), (0, 0, 0), (N, Cc, H, W)
+    if t.dtype != torch.float32:
+        raise ValueError(f'val_metrics: {name} is {t.dtype}; float32 planes or uint8 bytes')
+    if t.stride(3) != 1:
+        t = t.contiguous()
+    return t, t.data_ptr(), 0, (t.stride(0), t.stride(1), t.stride(2)), tuple(t.shape)
+
+
+def val_metrics(pred, gt, crop_border=0, swap_rb=True, what=('psnr', 'ssim'), want_y=False):
+    """The validation metrics of `use_image: true` from device tensors, N images in one call, nothing synchronised (csrc/tdr_valmetrics.hip).
+    pred / gt: float32 [N,C,H,W] (any image / channel / row strides, unit pixel stride: a slice of a padded output goes in as it is;
+    quantised as planes_to_img_u8 quantises, `swap_rb` = tensor2img's rgb2bgr) or uint8 [N,H,W,C] (taken as they are), C in {1, 3}.
+    what: names out of 'psnr', 'ssim', 'psnr_y', 'ssim_y', 'y' (the Y planes alone).  -> float64 [N, 8] on the device, columns VALM_S (the
+    exact squared byte error), VALM_MAX (largest byte of pred), VALM_COUNT, VALM_SSIM3D (ssim3d's value), VALM_SY (squared Y error),
+    VALM_COUNT_Y, VALM_SSIMY (ssim_y64's value); with want_y also the two Y planes, float32 [N, H - 2 crop, W - 2 crop]."""
+    mask = 0
+    for w in ((what,) if isinstance(what, str) else what):
+        if w not in VALM_WHAT:
+            raise ValueError(f'val_metrics: unknown entry {w!r} in what; known: {sorted(VALM_WHAT)}')
+        mask |= VALM_WHAT[w]
+    pk, pf, pu, ps, pshape = _valm_source(pred, 'pred')
+    gk, gf, gu, gs, gshape = _valm_source(gt, 'gt')
+    if pshape != gshape or pred.device != gt.device:
+        raise ValueError(f'val_metrics: pred is N,C,H,W = {pshape}, gt {gshape}: one shape and one device')
+    N, Cc, H, W = pshape
+    crop = int(crop_border)
+    lib = _lib.load()
+    ya = yb = None
+    if want_y or (mask & VALM_Y_PLANES):
+        ya = torch.empty(N, max(H - 2 * crop, 0), max(W - 2 * crop, 0), dtype=torch.float32, device=pred.device)
+        yb = torch.empty_like(ya)
+    ws = workspace((lib.tdr_val_metrics_ws_bytes(N, H, W) + 3) // 4, pred.device, 'valm')
+    out = torch.empty(N, 8, dtype=torch.float64, device=pred.device)
+    check(lib.tdr_val_metrics(pf, pu, ps[0], ps[1], ps[2], gf, gu, gs[0], gs[1], gs[2], N, Cc, H, W, crop, int(bool(swap_rb)), mask,
+                              _p(ya), _p(yb), ws.data_ptr(), out.data_ptr(), _stream()), 'tdr_val_metrics')
+    return (out, ya, yb) if ya is not None else out
+
+
 _niqe_host_tables = None
 _niqe_tables = {}
 

@@ -98,3 +98,5 @@ def calculate_ssim(img1, img2, crop_border, input_order='HWC', test_y_channel=Fa
 
 
 from .niqe import calculate_niqe, niqe, niqe_from_features, reorder_image  # noqa: E402  (niqe.py uses to_y_channel from above)
+from . import device  # noqa: E402,F401  (the same two metrics from device tensors: metrics.device.ValMetrics / psnr_ssim)
+from .device import ValMetrics  # noqa: E402,F401

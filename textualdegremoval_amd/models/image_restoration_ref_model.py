@@ -492,7 +492,31 @@ class RefGuidedImageCleanModel(BaseModel):
         finally:
             self._val_refreshed = False
 
+    def _validate_device(self, dataloader, test, rgb2bgr, use_image):
+        """`val: {device_metrics: true}`: the restored image and its ground truth stay on the device (metrics.device.ValMetrics: quantised,
+        cropped, compared and reduced there, whatever slice or session buffer self.output is), the numbers come back once after the loop --
+        the same `metric_results`, bit for bit, as the host loop below gives for `use_image: true`."""
+        from ..metrics.device import ValMetrics
+        if not use_image:
+            raise ValueError('val.device_metrics compares the byte images of `use_image: true` validation; with use_image: false the metrics '
+                             'are taken on the float tensors -- drop one of the two')
+        acc = ValMetrics(self.opt['val']['metrics'])               # (refuses a metric type without a device path)
+        for val_data in dataloader:
+            if 'gt' not in val_data:
+                raise ValueError('val.device_metrics needs a ground truth: this validation batch has no `gt` to compare the output with')
+            self.feed_data(val_data)
+            test()
+            acc.add(self.output, self.gt, rgb2bgr)
+        self.metric_results = acc.result()
+        current_metric = 0.
+        for m in self.metric_results:
+            current_metric = self.metric_results[m]
+        logger.info('Validation ' + ', '.join(f'{m}: {v:.4f}' for m, v in self.metric_results.items()))
+        return current_metric
+
     def _validate(self, dataloader, test, with_metrics, rgb2bgr, use_image):
+        if with_metrics and (self.opt.get('val') or {}).get('device_metrics'):
+            return self._validate_device(dataloader, test, rgb2bgr, use_image)
         cnt = 0
         for val_data in dataloader:
             self.feed_data(val_data)
