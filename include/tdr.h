@@ -26,7 +26,7 @@ extern "C" {
  * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8, then
  * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL, then tdr_tile_gather /
  * tdr_tile_blend, then tdr_window_resize_bilinear / tdr_token_match_bank, then tdr_dihedral_gather / tdr_dihedral_mean, then
- * tdr_val_metrics_ws_bytes / tdr_val_metrics -- no existing entry point
+ * tdr_val_metrics_ws_bytes / tdr_val_metrics, then tdr_ssim_loss_ws_bytes / tdr_ssim_loss -- no existing entry point
  * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there).
  * This header is the only written copy of the ABI: the binding (textualdegremoval_amd/_lib.py) derives its ctypes structs, argument lists and
  * version number from the text below at import and refuses a library whose tdr_version() differs.  Its parser knows the C this file uses and
@@ -529,6 +529,33 @@ int tdr_l1_loss_guarded(const float* pred, const float* target, int64_t numel, f
  * * dloss/dpred; ws: 2*1024 + 2*64*N floats. */
 int tdr_pixel_loss(int kind, const float* pred, const float* target, int N, int64_t chw, int64_t hw, float loss_weight, float eps,
                    float grad_scale, const TdrStepGuard* guard, float* loss, float* dpred, float* ws, void* stream);
+
+/* SSIMLoss: the validation SSIM as a training criterion, value + gradient (csrc/tdr_ssim_loss.hip; an addition to ABI 112).  The reference
+ * has no such criterion; the arithmetic is its metric's, metrics/psnr_ssim.py:131-176 (_ssim_3d), as tdr_ssim3d runs it.
+ * pred / target [N][C][H][W] float32 dense, C in 1 .. 4, finite.  For image n, SSIM_n is the mean over the H*W*C voxels of
+ *   S = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2)),
+ *   mu1 = G pred_n, mu2 = G target_n, s11 = G pred_n^2 - mu1^2, s22 = G target_n^2 - mu2^2, s12 = G (pred_n target_n) - mu1 mu2,
+ * G the separable 11-tap Gaussian (sigma 1.5, cv2.getGaussianKernel) along H, W and the channel axis with replicate borders on all three,
+ * C1 = (0.01 max_value)^2, C2 = (0.03 max_value)^2 with max_value an ARGUMENT (the metric's `1 if max <= 1 else 255` would put a jump into
+ * a criterion).  ssim: [N] floats, ssim[n] bit-identical to what tdr_ssim3d returns for the [H][W][C] images of the same floats (one
+ * workgroup body, the same tiles, partials and fold).  loss: 1 float = float32(double(loss_weight) * (1.0 - (sum_n double(ssim[n])) / N)),
+ * n ascending.
+ * dpred (NULL: the value only): [N][C][H][W],
+ *   term = scale * (-loss_weight / (N H W C)) * [ G^T(dS/dmu1) + 2 pred G^T(dS/dE11) + target G^T(dS/dE12) ],  E11 = G pred^2, E12 = G (pred target),
+ * G^T the adjoint of the replicate-border filter: along an axis of length L, (G^T p)[x] = sum_{y in [0,L), |y-x| <= 5} g[x-y+5] p[y], plus at
+ * x = 0 sum_{y < min(5,L)} p[y] sum_{k < 5-y} g[k], plus at x = L-1 sum_{y >= max(0,L-5)} p[y] sum_{k >= 6+(L-1-y)} g[k] (L = 1: both on the one
+ * element); the channel axis takes the transpose of its C x C matrix.  target receives no gradient.  scale = grad_scale (* guard->scale when
+ * guard != NULL), as in tdr_pixel_loss; a power of two scales dpred exactly.  accumulate != 0: dpred[i] = dpred[i] + term[i], one float32 add
+ * per element (a second criterion on the dpred of tdr_pixel_loss); otherwise a plain store.  The kernel evaluates the bracket in deviations,
+ * G^T(d) + 2 sum_y G^T[x,y] a[y] (pred[x] - mu1[y]) + sum_y G^T[x,y] b[y] (target[x] - mu2[y]) with a = dS/dE11, b = dS/dE12 and d the part of
+ * dS/dmu1 at fixed variances -- the same sum without the cancellation of parts ~ pred / C2.
+ * ws: tdr_ssim_loss_ws_bytes(N, C, H, W) bytes (16-byte aligned; 0 for C outside 1 .. 4 or N, H, W < 1): the per-tile partials and, for the gradient,
+ * five coefficient maps of the volume.  Bad arguments (C outside 1 .. 4, N, H or W < 1, N > 65535, NULL pred / target / loss / ssim / ws)
+ * return non-zero and launch nothing.  Two launches for the value, three with the gradient; no atomics, no host synchronisation: the same
+ * call gives the same bits. */
+int64_t tdr_ssim_loss_ws_bytes(int N, int C, int H, int W);
+int tdr_ssim_loss(const float* pred, const float* target, int N, int C, int H, int W, float max_value, float loss_weight, float grad_scale,
+                  const TdrStepGuard* guard, int accumulate, float* loss, float* ssim, float* dpred, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
  * MASA match-and-transfer (network_nafnet_guided_arch.py:495-707)

@@ -49,9 +49,18 @@ inline void ssim3d_fill(Ssim3dParams& p, int H, int W, int C) {
 inline float ssim3d_c1(float max_value) { return (0.01f * max_value) * (0.01f * max_value); }
 inline float ssim3d_c2(float max_value) { return (0.03f * max_value) * (0.03f * max_value); }
 
+// the sink of the plain kernels: nothing but the partial sums leaves the workgroup
+struct NoSink {
+    __device__ __forceinline__ void operator()(int, int, int, float, float, float, float, float) const {}
+};
+
 // ld.a(y, x, j) / ld.b(y, x, j): sample of channel j at pixel (y, x) of the H x W image, as a float.  Writes partial[tile].
-template <int C, class Loader>
-__device__ __forceinline__ void ssim3d_tile(const Ssim3dParams& p, const float c1, const float c2, const Loader& ld, float* partial) {
+// sink(k, y, x, mu1, mu2, s11, s22, s12) sees the statistics of every voxel of the image after its SSIM value has joined the sum: the
+// UNSHIFTED means and the (shift-invariant) variances and covariance -- tdr_ssim_loss.hip turns them into the coefficient maps of the
+// backward pass.  It takes no part in the sum: the same samples give the same partials under every sink.
+template <int C, class Loader, class Sink>
+__device__ __forceinline__ void ssim3d_tile_sink(const Ssim3dParams& p, const float c1, const float c2, const Loader& ld, float* partial,
+                                                 const Sink& sink) {
     __shared__ float s0[NF][E][E + 1];
     __shared__ float s1[NF][E][T + 1];
     __shared__ float red[4];
@@ -103,6 +112,7 @@ __device__ __forceinline__ void ssim3d_tile(const Ssim3dParams& p, const float c
             const float mu1 = v[0] + ca, mu2 = v[1] + cb;
             const float m11 = mu1 * mu1, m22 = mu2 * mu2, m12 = mu1 * mu2;
             sum += ((2.f * m12 + c1) * (2.f * s12 + c2)) / ((m11 + m22 + c1) * (s11 + s22 + c2));
+            sink(k, y0 + ty, x0 + tx, mu1, mu2, s11, s22, s12);
         }
         __syncthreads();
     }
@@ -111,6 +121,11 @@ __device__ __forceinline__ void ssim3d_tile(const Ssim3dParams& p, const float c
     if ((tid & 63) == 0) red[tid >> 6] = sum;
     __syncthreads();
     if (tid == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+template <int C, class Loader>
+__device__ __forceinline__ void ssim3d_tile(const Ssim3dParams& p, const float c1, const float c2, const Loader& ld, float* partial) {
+    ssim3d_tile_sink<C>(p, c1, c2, ld, partial, NoSink{});
 }
 
 // the fold of n per-workgroup partials of ssim3d_tile by one 256-thread workgroup -> float32(sum * inv_count), valid in thread 0

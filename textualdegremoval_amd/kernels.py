@@ -1415,6 +1415,7 @@ def l1_loss(pred, target, loss_weight=1.0, grad_scale=1.0, guard=None):
 
 
 LOSS_L1, LOSS_MSE, LOSS_CHARBONNIER, LOSS_PSNR, LOSS_PSNR_Y = range(5)
+LOSS_SSIM = 100      # SSIMLoss.step_kind(): not a kind of tdr_pixel_loss -- the step calls ssim_loss (tdr_ssim_loss) for it
 
 
 def pixel_loss(kind, pred, target, loss_weight=1.0, eps=1e-3, grad_scale=1.0, guard=None):
@@ -1428,6 +1429,31 @@ def pixel_loss(kind, pred, target, loss_weight=1.0, eps=1e-3, grad_scale=1.0, gu
                                      float(grad_scale), guard.data_ptr() if guard is not None else None, loss.data_ptr(),
                                      dpred.data_ptr(), ws.data_ptr(), _stream()), 'tdr_pixel_loss')
     return loss, dpred
+
+
+def ssim_loss(pred, target, loss_weight=1.0, max_value=1.0, grad_scale=1.0, guard=None, dpred=None, want_grad=True):
+    """pred / target [N,C,H,W] float32, C <= 4 -> (loss [1], ssim [N], dpred): SSIMLoss, loss = w * (1 - mean_n SSIM_n) with SSIM_n the
+    bits of ssim3d on image n, and its gradient (csrc/tdr_ssim_loss.hip).  `dpred=` names a tensor the term is ADDED to (the dpred of
+    pixel_loss: one float32 add per element); want_grad=False computes the value alone and returns dpred as it came (None)."""
+    if not (pred.dim() == 4 and pred.shape == target.shape and pred.is_cuda and target.is_cuda
+            and pred.dtype == torch.float32 and target.dtype == torch.float32):
+        raise ValueError(f'ssim_loss: pred {tuple(pred.shape)} {pred.dtype}, target {tuple(target.shape)} {target.dtype}: '
+                         'two float32 [N,C,H,W] device tensors of one shape')
+    assert pred.is_contiguous() and target.is_contiguous()
+    N, Cc, H, W = pred.shape
+    lib = _lib.load()
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    ssim = torch.empty(max(N, 1), dtype=torch.float32, device=pred.device)[:N]
+    accumulate = dpred is not None
+    if accumulate:
+        assert want_grad and dpred.shape == pred.shape and dpred.dtype == torch.float32 and dpred.is_contiguous() and dpred.is_cuda
+    elif want_grad:
+        dpred = torch.empty_like(pred)
+    ws = workspace((lib.tdr_ssim_loss_ws_bytes(N, Cc, H, W) + 3) // 4, pred.device, 'ssim_loss')
+    check(lib.tdr_ssim_loss(pred.data_ptr(), target.data_ptr(), N, Cc, H, W, float(max_value), float(loss_weight), float(grad_scale),
+                            guard.data_ptr() if guard is not None else None, int(accumulate), loss.data_ptr(), ssim.data_ptr(),
+                            dpred.data_ptr() if want_grad else None, ws.data_ptr(), _stream()), 'tdr_ssim_loss')
+    return loss, ssim, dpred
 
 
 # ------------------------------------------------------------------ MASA

@@ -1,8 +1,14 @@
 """Pixel losses with the reference's names (losses/losses.py:26-122).  On the device every criterion with mean reduction is
 the HIP kernel tdr_pixel_loss (value + gradient in one pass); `step_kind()` tells the train step which one to fuse.  The
-torch expressions below serve host tensors and the weighted / 'none' / 'sum' variants no shipped YAML selects."""
+torch expressions below serve host tensors and the weighted / 'none' / 'sum' variants no shipped YAML selects.
+
+SSIMLoss is the project's own criterion (the reference trains on none): w * (1 - mean_n SSIM_n) with SSIM_n the validation metric's 11^3
+Gaussian SSIM over the [H,W,C] volume (metrics/psnr_ssim.py:131-176) at a FIXED max_value.  On the device it is the HIP kernel
+tdr_ssim_loss (value, and the gradient through the adjoint of the replicate-border filter); its `step_kind()` is (LOSS_SSIM, weight,
+max_value) and the train step fuses it alone (`pixel_opt`) or next to a pixel criterion (`ssim_opt`).  It has no ATen path on the device."""
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from .. import kernels as K
@@ -93,6 +99,63 @@ class PSNRLoss(nn.Module):
             pred = ((pred * coef).sum(dim=1, keepdim=True) + 16.) / 255.
             target = ((target * coef).sum(dim=1, keepdim=True) + 16.) / 255.
         return self.loss_weight * self.scale * torch.log(((pred - target) ** 2).mean(dim=(1, 2, 3)) + 1e-8).mean()
+
+
+class _SsimFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, loss_weight, max_value):
+        loss, _, dpred = K.ssim_loss(pred.contiguous(), target.contiguous(), loss_weight, max_value)
+        ctx.save_for_backward(dpred)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return dpred * g, None, None, None
+
+
+def _ssim_volume_filter(v, g):
+    """v [N,C,H,W] -> the 11-tap Gaussian along H, W and the channel axis of the [H,W,C] volume, replicate borders on all three"""
+    v = v.permute(0, 2, 3, 1).unsqueeze(1)               # [N,1,H,W,C]
+    for axis in (2, 3, 4):
+        pad = [0] * 6
+        pad[2 * (4 - axis)] = pad[2 * (4 - axis) + 1] = 5
+        shape = [1] * 5
+        shape[axis] = 11
+        v = F.conv3d(F.pad(v, pad, mode='replicate'), g.view(shape))
+    return v.squeeze(1)
+
+
+class SSIMLoss(nn.Module):
+    """w * (1 - mean over images of SSIM_n): SSIM_n the mean of the SSIM map of the [H,W,C] volume under the 11^3 Gaussian window
+    (sigma 1.5, replicate borders) -- calculate_ssim's arithmetic with C1 = (0.01 max_value)^2, C2 = (0.03 max_value)^2 at the FIXED
+    max_value given here (the metric's `1 if max <= 1 else 255` would put a jump into a criterion).  pred receives the gradient."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean', max_value=1.0):
+        super().__init__()
+        assert reduction == 'mean'
+        self.loss_weight, self.max_value = loss_weight, max_value
+
+    def step_kind(self):
+        return (K.LOSS_SSIM, float(self.loss_weight), float(self.max_value))
+
+    def forward(self, pred, target):
+        if pred.is_cuda or target.is_cuda:
+            if not (_on_device(pred, target) and target.is_cuda and pred.shape == target.shape and 1 <= pred.shape[1] <= 4):
+                raise ValueError(f'SSIMLoss on the device takes float32 [N,C,H,W] tensors of one shape with C <= 4 (tdr_ssim_loss), not '
+                                 f'pred {tuple(pred.shape)} {pred.dtype} / target {tuple(target.shape)} {target.dtype}')
+            return _SsimFn.apply(pred, target, float(self.loss_weight), float(self.max_value))
+        assert pred.dim() == 4 and pred.shape == target.shape
+        x = torch.arange(11, dtype=torch.float64) - 5
+        g = torch.exp(-(x * x) / (2 * 1.5 * 1.5))
+        g = (g / g.sum()).to(pred.dtype)
+        c1, c2 = (0.01 * self.max_value) ** 2, (0.03 * self.max_value) ** 2
+        mu1, mu2 = _ssim_volume_filter(pred, g), _ssim_volume_filter(target, g)
+        s11 = _ssim_volume_filter(pred * pred, g) - mu1 * mu1
+        s22 = _ssim_volume_filter(target * target, g) - mu2 * mu2
+        s12 = _ssim_volume_filter(pred * target, g) - mu1 * mu2
+        smap = ((2 * mu1 * mu2 + c1) * (2 * s12 + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (s11 + s22 + c2))
+        return self.loss_weight * (1 - smap.flatten(1).mean(1).mean())
 
 
 class CharbonnierLoss(nn.Module):

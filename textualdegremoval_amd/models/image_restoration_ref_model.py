@@ -65,6 +65,15 @@ class RefGuidedImageCleanModel(BaseModel):
             self.cri_pix = getattr(loss_module, pixel_type)(**train_opt['pixel_opt']).to(self.device)
         else:
             raise ValueError('pixel loss are None.')
+        # train.ssim_opt: {type: SSIMLoss, loss_weight, max_value} -- a structural term ADDED to whatever pixel_opt names (this
+        # project's key: the reference trains on the pixel criterion alone); the step fuses it into the same dpred
+        self.cri_ssim = None
+        if train_opt.get('ssim_opt'):
+            ssim_opt = dict(train_opt['ssim_opt'])
+            ssim_type = ssim_opt.pop('type', None)
+            if ssim_type != 'SSIMLoss':
+                raise ValueError(f"train.ssim_opt.type is {ssim_type!r}: the structural term is 'SSIMLoss'")
+            self.cri_ssim = loss_module.SSIMLoss(**ssim_opt).to(self.device)
         self.setup_optimizers()
         self.setup_schedulers()
 
@@ -166,7 +175,10 @@ class RefGuidedImageCleanModel(BaseModel):
             loss = self._graph_step()
         else:
             loss = self._eager_step(self.lq, self.gt, self.ref_in)
-        self.log_dict = self.reduce_loss_dict(OrderedDict(l_pix=loss[0]))
+        losses = OrderedDict(l_pix=loss[0])
+        if self._loss_ssim is not None:        # train.ssim_opt: the structural term, logged next to the pixel criterion alone
+            losses['l_ssim'] = self._loss_ssim[0]
+        self.log_dict = self.reduce_loss_dict(losses)
         if self.ema_decay > 0:
             self.model_ema(decay=self.ema_decay)
 
@@ -241,15 +253,24 @@ class RefGuidedImageCleanModel(BaseModel):
         prev_scaled = K.GRAD_SCALED
         try:
             kind, lw, eps = self.cri_pix.step_kind()
+            ssim_term = self.cri_ssim.step_kind()[1:] if getattr(self, 'cri_ssim', None) is not None else None   # (weight, max_value)
+            lw_scale = lw                      # the weight the starting loss-scale exponent is computed from
+            if kind == K.LOSS_SSIM or ssim_term is not None:
+                # an SSIM gradient is not flat like L1's: max|dpred| * numel was 3.4 - 22.8 at w = 1 on the host reference's cases against
+                # exactly 1 for L1, 2^4.5 rounded up = 32.  The larger term sets the starting exponent (0 for a term that is absent);
+                # a starting value only -- the first-step survey and the step guard move it as they do for PSNRLoss's -8
+                lw_pix = 0.0 if kind == K.LOSS_SSIM else lw
+                lw_ssim = (lw if kind == K.LOSS_SSIM else 0.0) + (ssim_term[0] if ssim_term is not None else 0.0)
+                lw_scale = max(lw_pix, 32.0 * lw_ssim)
             # exact (power-of-two) loss scale for the fp16-split data-gradient kernels: dpred = S*lw/numel ~ 2^9, which puts
             # max|g| of every gradient operand of the step between ~2^-1 and 2^10 (profiles/grad_range_survey.py)
             # The scale lives in the optimiser's device-resident StepGuard: a non-finite gradient norm (an operand left the
             # fp16 range) skips that step and halves it, 1000 finite steps double it again up to this starting value.
             gs = 1.0
-            if K.fp16_path() and GRAD_SCALE and lw > 0 and \
+            if K.fp16_path() and GRAD_SCALE and lw_scale > 0 and \
                     not getattr(self, '_bwd_full_range', False):
                 # PSNRLoss: dpred ~ lw*(10/ln10)*2d / (N*CHW*mse_n), ~2^8 above an L1 gradient at d ~ 0.1: start lower
-                gs = 2.0 ** (math.floor(math.log2(512.0 * lq.shape[0] * 3 * lq.shape[2] * lq.shape[3] / lw)) +
+                gs = 2.0 ** (math.floor(math.log2(512.0 * lq.shape[0] * 3 * lq.shape[2] * lq.shape[3] / lw_scale)) +
                              getattr(self, '_scale_shift', 0) - (8 if kind in (K.LOSS_PSNR, K.LOSS_PSNR_Y) else 0))
             K.set_grad_scaled(gs != 1.0)
             guard = self.optimizer_g.ensure_guard(lq.device)
@@ -265,7 +286,14 @@ class RefGuidedImageCleanModel(BaseModel):
             eng = getattr(net, 'engine', E)    # RestormerRefFusion carries restormer_engine
             out, saved = eng.net_fwd(P, net.cfg, lq, ref_in)
             self.output = out
-            loss, dpred = K.pixel_loss(kind, out.contiguous(), gt.contiguous(), lw, eps, guard=guard)
+            out_c, gt_c = out.contiguous(), gt.contiguous()
+            if kind == K.LOSS_SSIM:            # pixel_opt: {type: SSIMLoss}: step_kind()'s third entry is its max_value
+                loss, _, dpred = K.ssim_loss(out_c, gt_c, lw, eps, guard=guard)
+            else:
+                loss, dpred = K.pixel_loss(kind, out_c, gt_c, lw, eps, guard=guard)
+            self._loss_ssim = None
+            if ssim_term is not None:          # ssim_opt: the structural term joins the same dpred, one float32 add per element
+                self._loss_ssim, _, dpred = K.ssim_loss(out_c, gt_c, ssim_term[0], ssim_term[1], guard=guard, dpred=dpred)
             sink = self.grad_reducer.begin(defer_collectives=defer_collectives, on_bucket=on_bucket)
             K.BACKWARD_PHASE = True
             try:
@@ -376,7 +404,7 @@ class RefGuidedImageCleanModel(BaseModel):
                     gB.capture_end()
             torch.cuda.current_stream().wait_stream(cap)
             st['segs'], st['gB'], st['split'] = segs, gB, split
-            st['output'] = self.output
+            st['output'], st['loss_ssim'] = self.output, self._loss_ssim
         else:
             st['lq'].copy_(self.lq, non_blocking=True)
             st['gt'].copy_(self.gt, non_blocking=True)
@@ -391,10 +419,11 @@ class RefGuidedImageCleanModel(BaseModel):
         else:
             red.allreduce_flat()
         st['gB'].replay()
-        self.output = st['output']
+        self.output, self._loss_ssim = st['output'], st['loss_ssim']
         return st['loss']
 
     skipped_steps = 0
+    _loss_ssim = None       # the [1] loss tensor of train.ssim_opt's term of the last step (None without the block)
 
     def get_current_log(self):
         """the base class's floats (a non-finite loss raises there); also the place where skipped optimiser steps become
