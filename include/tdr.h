@@ -26,7 +26,8 @@ extern "C" {
  * additions only: tdr_conv1x1_bx3_staged_set / tdr_conv1x1_bx3_staged_takes, then tdr_img_u8_to_planes / tdr_planes_to_img_u8, then
  * tdr_sf_act_region_sums / tdr_sf_act_region_apply and a `low` of tdr_sf_dynfilt_fwd that may be NULL, then tdr_tile_gather /
  * tdr_tile_blend, then tdr_window_resize_bilinear / tdr_token_match_bank, then tdr_dihedral_gather / tdr_dihedral_mean, then
- * tdr_val_metrics_ws_bytes / tdr_val_metrics, then tdr_ssim_loss_ws_bytes / tdr_ssim_loss -- no existing entry point
+ * tdr_val_metrics_ws_bytes / tdr_val_metrics, then tdr_ssim_loss_ws_bytes / tdr_ssim_loss, then tdr_freq_loss_takes /
+ * tdr_freq_loss_ws_bytes / tdr_freq_loss -- no existing entry point
  * or descriptor changed, and the binding resolves every declared symbol when it loads the library, so a build without them is refused there).
  * This header is the only written copy of the ABI: the binding (textualdegremoval_amd/_lib.py) derives its ctypes structs, argument lists and
  * version number from the text below at import and refuses a library whose tdr_version() differs.  Its parser knows the C this file uses and
@@ -556,6 +557,40 @@ int tdr_pixel_loss(int kind, const float* pred, const float* target, int N, int6
 int64_t tdr_ssim_loss_ws_bytes(int N, int C, int H, int W);
 int tdr_ssim_loss(const float* pred, const float* target, int N, int C, int H, int W, float max_value, float loss_weight, float grad_scale,
                   const TdrStepGuard* guard, int accumulate, float* loss, float* ssim, float* dpred, void* ws, void* stream);
+
+/* FFTLoss: the frequency-domain L1 criterion, value + gradient (csrc/tdr_freq_loss.hip; an addition to ABI 112).  The reference has no
+ * such criterion; it is the `L1 + 0.1 |FFT2(pred) - FFT2(gt)|_1` term SFNet / MIMO-UNet are trained with (onesided = 0) and the rfft2
+ * `FFTLoss` of the BasicSR forks (onesided = 1).
+ * pred / target [N][C][H][W] float32 dense; P = N C planes, each independent.  d = pred - target, one float32 subtraction.
+ *   D[ky,kx] = sum_{y,x} d[y,x] exp(-2 pi i (ky y / H + kx x / W)), unnormalised; only the half spectrum kx in [0, W/2] is ever formed
+ * (Hermitian symmetry).  The four self-conjugate bins, ky in {0, H/2} crossed with kx in {0, W/2}, have their imaginary part taken as
+ * exactly 0, in the value and in the gradient.  sgn(+-0) = 0.
+ * onesided = 0 (two-sided: w * mean | stack(fft2(pred).real, .imag) - stack(fft2(target).real, .imag) |):
+ *   loss = w * sum_{p, ky, kx <= W/2} c[kx] (|Re D| + |Im D|) / count,  c = 1 at kx in {0, W/2}, 2 elsewhere,  count = 2 P H W.
+ * onesided = 1 (the same mean over rfft2): c = 1 everywhere, count = 2 P H (W/2 + 1).
+ * loss: 1 float = float32(double(loss_weight) * S / count); S is folded from per-workgroup partials (doubles) in a fixed order, the last
+ * fold in double; no atomics: the same call gives the same bits.
+ * dpred (NULL: the value only, nothing is written back): [N][C][H][W],
+ *   dpred[p] = scale * (loss_weight / count) * c2r(Gh),  Gh[ky,kx] = m[kx] (sgn Re D + i sgn Im D),
+ * c2r the unnormalised inverse real transform (irfft2(..., norm='forward'): the inverse complex transform along H, then along W the
+ * Hermitian extension of the half spectrum, the imaginary parts of kx = 0 and W/2 ignored); m = 1 for onesided = 0; for onesided = 1
+ * m = 1 at kx in {0, W/2} and 1/2 elsewhere.  target receives no gradient.  scale = grad_scale (* guard->scale when guard != NULL), as in
+ * tdr_pixel_loss; a power of two scales dpred exactly.  accumulate != 0: dpred[i] = dpred[i] + term[i], one float32 add per element (a
+ * further criterion on the dpred of tdr_pixel_loss / tdr_ssim_loss); otherwise a plain store.
+ * spec (NULL, or [P][H][W/2+1][2] floats): D as the kernel decided on it -- (Re, Im) per bin in natural (ky, kx) order, the imaginary
+ * parts of the self-conjugate bins already 0; the signs of these floats are the signs the gradient carries.
+ * Admissible lengths: H and W each m * 2^a with m in {1, 3, 5}, a >= 2, 4 <= length <= 1024 (64, 96, 128, 160, 192, 256, 320, 384, 512,
+ * ...); anything else is refused, never padded -- padding changes the criterion.  tdr_freq_loss_takes(H, W): 1 / 0 by that rule (host
+ * only, no device needed).  ws: tdr_freq_loss_ws_bytes(N, C, H, W) bytes (16-byte aligned; 0 for anything refused): the two twiddle
+ * tables exp(-2 pi i t / L) (computed in double, rounded once), two digit-reversal index tables, the partials, and the half spectrum
+ * [P][H][W/2+1] complex.
+ * Bad arguments (an inadmissible H or W, N or C < 1, N * C > 65535 planes -- the plane is a grid y index --, NULL pred / target / loss /
+ * ws) return non-zero and launch nothing.  Four launches for the value (tables, rows, columns with the partial sums, finish), five with
+ * the gradient (rows back); no atomics, no host synchronisation, capturable. */
+int tdr_freq_loss_takes(int H, int W);
+int64_t tdr_freq_loss_ws_bytes(int N, int C, int H, int W);
+int tdr_freq_loss(const float* pred, const float* target, int N, int C, int H, int W, int onesided, float loss_weight, float grad_scale,
+                  const TdrStepGuard* guard, int accumulate, float* loss, float* dpred, float* spec, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
  * MASA match-and-transfer (network_nafnet_guided_arch.py:495-707)

@@ -1416,6 +1416,7 @@ def l1_loss(pred, target, loss_weight=1.0, grad_scale=1.0, guard=None):
 
 LOSS_L1, LOSS_MSE, LOSS_CHARBONNIER, LOSS_PSNR, LOSS_PSNR_Y = range(5)
 LOSS_SSIM = 100      # SSIMLoss.step_kind(): not a kind of tdr_pixel_loss -- the step calls ssim_loss (tdr_ssim_loss) for it
+LOSS_FREQ = 101      # FFTLoss.step_kind(): likewise -- the step calls freq_loss (tdr_freq_loss) for it
 
 
 def pixel_loss(kind, pred, target, loss_weight=1.0, eps=1e-3, grad_scale=1.0, guard=None):
@@ -1454,6 +1455,44 @@ def ssim_loss(pred, target, loss_weight=1.0, max_value=1.0, grad_scale=1.0, guar
                             guard.data_ptr() if guard is not None else None, int(accumulate), loss.data_ptr(), ssim.data_ptr(),
                             dpred.data_ptr() if want_grad else None, ws.data_ptr(), _stream()), 'tdr_ssim_loss')
     return loss, ssim, dpred
+
+
+FREQ_LENGTHS = 'H and W each m * 2^a with m in {1, 3, 5}, a >= 2, 4 <= length <= 1024 (64, 96, 128, 160, 192, 256, 320, 384, 512, ...)'
+
+
+def freq_loss_takes(H, W):
+    """tdr_freq_loss's rule for the two transform lengths (no device needed)"""
+    return bool(_lib.load().tdr_freq_loss_takes(int(H), int(W)))
+
+
+def freq_loss(pred, target, loss_weight=1.0, onesided=False, grad_scale=1.0, guard=None, dpred=None, want_grad=True,
+              want_spectrum=False):
+    """pred / target [N,C,H,W] float32 -> (loss [1], dpred) or (loss, dpred, spec [N*C,H,W/2+1,2]): FFTLoss, loss = w * mean |Re, Im of
+    fft2(pred) - fft2(target)| (rfft2 with onesided), and its gradient (csrc/tdr_freq_loss.hip).  `dpred=` names a tensor the term is
+    ADDED to (the dpred of pixel_loss / ssim_loss: one float32 add per element); want_grad=False computes the value alone and returns
+    dpred as it came (None); want_spectrum=True also returns the difference spectrum as the kernel decided on it."""
+    if not (pred.dim() == 4 and pred.shape == target.shape and pred.is_cuda and target.is_cuda
+            and pred.dtype == torch.float32 and target.dtype == torch.float32):
+        raise ValueError(f'freq_loss: pred {tuple(pred.shape)} {pred.dtype}, target {tuple(target.shape)} {target.dtype}: '
+                         f'two float32 [N,C,H,W] device tensors of one shape, {FREQ_LENGTHS}')
+    N, Cc, H, W = pred.shape
+    lib = _lib.load()
+    if not (N >= 1 and Cc >= 1 and lib.tdr_freq_loss_takes(H, W)):
+        raise ValueError(f'freq_loss: pred {tuple(pred.shape)}: {FREQ_LENGTHS}; other sizes are refused, not padded')
+    assert pred.is_contiguous() and target.is_contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    accumulate = dpred is not None
+    if accumulate:
+        assert want_grad and dpred.shape == pred.shape and dpred.dtype == torch.float32 and dpred.is_contiguous() and dpred.is_cuda
+    elif want_grad:
+        dpred = torch.empty_like(pred)
+    spec = torch.empty(N * Cc, H, W // 2 + 1, 2, dtype=torch.float32, device=pred.device) if want_spectrum else None
+    ws = workspace((lib.tdr_freq_loss_ws_bytes(N, Cc, H, W) + 3) // 4, pred.device, 'freq_loss')
+    check(lib.tdr_freq_loss(pred.data_ptr(), target.data_ptr(), N, Cc, H, W, int(bool(onesided)), float(loss_weight), float(grad_scale),
+                            guard.data_ptr() if guard is not None else None, int(accumulate), loss.data_ptr(),
+                            dpred.data_ptr() if want_grad else None, spec.data_ptr() if want_spectrum else None, ws.data_ptr(),
+                            _stream()), 'tdr_freq_loss')
+    return (loss, dpred, spec) if want_spectrum else (loss, dpred)
 
 
 # ------------------------------------------------------------------ MASA

@@ -5,7 +5,13 @@ torch expressions below serve host tensors and the weighted / 'none' / 'sum' var
 SSIMLoss is the project's own criterion (the reference trains on none): w * (1 - mean_n SSIM_n) with SSIM_n the validation metric's 11^3
 Gaussian SSIM over the [H,W,C] volume (metrics/psnr_ssim.py:131-176) at a FIXED max_value.  On the device it is the HIP kernel
 tdr_ssim_loss (value, and the gradient through the adjoint of the replicate-border filter); its `step_kind()` is (LOSS_SSIM, weight,
-max_value) and the train step fuses it alone (`pixel_opt`) or next to a pixel criterion (`ssim_opt`).  It has no ATen path on the device."""
+max_value) and the train step fuses it alone (`pixel_opt`) or next to a pixel criterion (`ssim_opt`).  It has no ATen path on the device.
+
+FFTLoss is the frequency-domain L1 term SFNet / MIMO-UNet (`L1 + 0.1 FFTLoss`, at three scales) and the BasicSR forks (DeepRFT's rfft2
+form: onesided=True) are trained with: w * mean |stack(Re, Im)(fft2(pred) - fft2(target))|.  On the device it is the HIP kernel
+tdr_freq_loss -- a hand-written 2-D real FFT for lengths m 2^a, m in {1, 3, 5}, 4 ... 1024, value and gradient; its `step_kind()` is
+(LOSS_FREQ, weight, onesided) and the train step fuses it alone (`pixel_opt`) or next to the other criteria (`freq_opt`).  Host tensors
+take the literal torch.fft expression; on the device it has no ATen path either."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -156,6 +162,47 @@ class SSIMLoss(nn.Module):
         s12 = _ssim_volume_filter(pred * target, g) - mu1 * mu2
         smap = ((2 * mu1 * mu2 + c1) * (2 * s12 + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (s11 + s22 + c2))
         return self.loss_weight * (1 - smap.flatten(1).mean(1).mean())
+
+
+class _FreqFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, loss_weight, onesided):
+        # (no gradient asked for -- a criterion evaluated for its value: the value-only launches, the same loss bits)
+        loss, dpred = K.freq_loss(pred.contiguous(), target.contiguous(), loss_weight, onesided, want_grad=ctx.needs_input_grad[0])
+        if dpred is not None:
+            ctx.save_for_backward(dpred)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return dpred * g, None, None, None
+
+
+class FFTLoss(nn.Module):
+    """w * mean |stack(fft2(pred).real, fft2(pred).imag) - stack(fft2(target).real, fft2(target).imag)| over the last two axes (the SFNet /
+    MIMO-UNet term); onesided=True takes rfft2 instead (the BasicSR forks).  On the device: tdr_freq_loss, for H and W each m 2^a with m
+    in {1, 3, 5}, a >= 2, 4 ... 1024 -- other sizes are refused, never padded (padding changes the criterion).  pred receives the gradient."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean', onesided=False):
+        super().__init__()
+        assert reduction == 'mean'
+        self.loss_weight, self.onesided = loss_weight, bool(onesided)
+
+    def step_kind(self):
+        return (K.LOSS_FREQ, float(self.loss_weight), float(self.onesided))
+
+    def forward(self, pred, target):
+        if pred.is_cuda or target.is_cuda:
+            if not (_on_device(pred, target) and target.is_cuda and pred.shape == target.shape
+                    and K.freq_loss_takes(pred.shape[2], pred.shape[3])):
+                raise ValueError(f'FFTLoss on the device takes float32 [N,C,H,W] tensors of one shape with {K.FREQ_LENGTHS} '
+                                 f'(tdr_freq_loss), not pred {tuple(pred.shape)} {pred.dtype} / target {tuple(target.shape)} {target.dtype}')
+            return _FreqFn.apply(pred, target, float(self.loss_weight), self.onesided)
+        assert pred.dim() == 4 and pred.shape == target.shape
+        fft = torch.fft.rfft2 if self.onesided else torch.fft.fft2
+        fp, ft = fft(pred), fft(target)
+        return self.loss_weight * (torch.stack([fp.real, fp.imag], -1) - torch.stack([ft.real, ft.imag], -1)).abs().mean()
 
 
 class CharbonnierLoss(nn.Module):

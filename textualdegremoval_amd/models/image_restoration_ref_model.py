@@ -74,6 +74,15 @@ class RefGuidedImageCleanModel(BaseModel):
             if ssim_type != 'SSIMLoss':
                 raise ValueError(f"train.ssim_opt.type is {ssim_type!r}: the structural term is 'SSIMLoss'")
             self.cri_ssim = loss_module.SSIMLoss(**ssim_opt).to(self.device)
+        # train.freq_opt: {type: FFTLoss, loss_weight, onesided} -- the frequency-domain L1 term of the SFNet / MIMO-UNet recipe
+        # (L1 + 0.1 FFTLoss), ADDED to whatever pixel_opt (and ssim_opt) name: pixel -> ssim -> freq, all into one dpred
+        self.cri_freq = None
+        if train_opt.get('freq_opt'):
+            freq_opt = dict(train_opt['freq_opt'])
+            freq_type = freq_opt.pop('type', None)
+            if freq_type != 'FFTLoss':
+                raise ValueError(f"train.freq_opt.type is {freq_type!r}: the frequency term is 'FFTLoss'")
+            self.cri_freq = loss_module.FFTLoss(**freq_opt).to(self.device)
         self.setup_optimizers()
         self.setup_schedulers()
 
@@ -178,6 +187,8 @@ class RefGuidedImageCleanModel(BaseModel):
         losses = OrderedDict(l_pix=loss[0])
         if self._loss_ssim is not None:        # train.ssim_opt: the structural term, logged next to the pixel criterion alone
             losses['l_ssim'] = self._loss_ssim[0]
+        if self._loss_freq is not None:        # train.freq_opt: the frequency term, likewise
+            losses['l_freq'] = self._loss_freq[0]
         self.log_dict = self.reduce_loss_dict(losses)
         if self.ema_decay > 0:
             self.model_ema(decay=self.ema_decay)
@@ -262,6 +273,19 @@ class RefGuidedImageCleanModel(BaseModel):
                 lw_pix = 0.0 if kind == K.LOSS_SSIM else lw
                 lw_ssim = (lw if kind == K.LOSS_SSIM else 0.0) + (ssim_term[0] if ssim_term is not None else 0.0)
                 lw_scale = max(lw_pix, 32.0 * lw_ssim)
+            freq_term = self.cri_freq.step_kind()[1:] if getattr(self, 'cri_freq', None) is not None else None   # (weight, onesided)
+            if kind == K.LOSS_FREQ or freq_term is not None:
+                fh, fw = int(gt.shape[-2]), int(gt.shape[-1])
+                if not K.freq_loss_takes(fh, fw):      # here, on the first step, and never as a TdrError inside a capture
+                    raise ValueError(f'FFTLoss: the output is {fh} x {fw}; {K.FREQ_LENGTHS} -- other sizes are refused, not padded')
+                # an FFT-L1 gradient is not flat either: c2r of +-1 per bin is a sum of 2 H W random signs, so max|dpred| * numel / w grows
+                # like sqrt(H W): 1.5 - 3.45 sqrt(H W) on the host reference's 12 cases, two-sided (3.1 - 3.45 from 64 x 64 up; one-sided:
+                # 1.7 - 3.6; the last column of profiles/freq_loss/errors.txt), hence 4 sqrt(H W).
+                # The largest term sets the starting exponent; a starting value only, as above
+                lw_freq = (lw if kind == K.LOSS_FREQ else 0.0) + (freq_term[0] if freq_term is not None else 0.0)
+                if kind == K.LOSS_FREQ:        # lw is the frequency term's weight, not a pixel criterion's
+                    lw_scale = 32.0 * ssim_term[0] if ssim_term is not None else 0.0
+                lw_scale = max(lw_scale, 4.0 * math.sqrt(fh * fw) * lw_freq)
             # exact (power-of-two) loss scale for the fp16-split data-gradient kernels: dpred = S*lw/numel ~ 2^9, which puts
             # max|g| of every gradient operand of the step between ~2^-1 and 2^10 (profiles/grad_range_survey.py)
             # The scale lives in the optimiser's device-resident StepGuard: a non-finite gradient norm (an operand left the
@@ -272,6 +296,8 @@ class RefGuidedImageCleanModel(BaseModel):
                 # PSNRLoss: dpred ~ lw*(10/ln10)*2d / (N*CHW*mse_n), ~2^8 above an L1 gradient at d ~ 0.1: start lower
                 gs = 2.0 ** (math.floor(math.log2(512.0 * lq.shape[0] * 3 * lq.shape[2] * lq.shape[3] / lw_scale)) +
                              getattr(self, '_scale_shift', 0) - (8 if kind in (K.LOSS_PSNR, K.LOSS_PSNR_Y) else 0))
+            if getattr(self, 'loss_scale_start', None) is None:
+                self.loss_scale_start = gs     # what the first step started from, before any survey moved it (probes and tests read it)
             K.set_grad_scaled(gs != 1.0)
             guard = self.optimizer_g.ensure_guard(lq.device)
             if not torch.cuda.is_current_stream_capturing():
@@ -289,11 +315,16 @@ class RefGuidedImageCleanModel(BaseModel):
             out_c, gt_c = out.contiguous(), gt.contiguous()
             if kind == K.LOSS_SSIM:            # pixel_opt: {type: SSIMLoss}: step_kind()'s third entry is its max_value
                 loss, _, dpred = K.ssim_loss(out_c, gt_c, lw, eps, guard=guard)
+            elif kind == K.LOSS_FREQ:          # pixel_opt: {type: FFTLoss}: step_kind()'s third entry is its onesided flag
+                loss, dpred = K.freq_loss(out_c, gt_c, lw, bool(eps), guard=guard)
             else:
                 loss, dpred = K.pixel_loss(kind, out_c, gt_c, lw, eps, guard=guard)
             self._loss_ssim = None
             if ssim_term is not None:          # ssim_opt: the structural term joins the same dpred, one float32 add per element
                 self._loss_ssim, _, dpred = K.ssim_loss(out_c, gt_c, ssim_term[0], ssim_term[1], guard=guard, dpred=dpred)
+            self._loss_freq = None
+            if freq_term is not None:          # freq_opt: the frequency term joins the same dpred, one float32 add per element
+                self._loss_freq, dpred = K.freq_loss(out_c, gt_c, freq_term[0], bool(freq_term[1]), guard=guard, dpred=dpred)
             sink = self.grad_reducer.begin(defer_collectives=defer_collectives, on_bucket=on_bucket)
             K.BACKWARD_PHASE = True
             try:
@@ -404,7 +435,7 @@ class RefGuidedImageCleanModel(BaseModel):
                     gB.capture_end()
             torch.cuda.current_stream().wait_stream(cap)
             st['segs'], st['gB'], st['split'] = segs, gB, split
-            st['output'], st['loss_ssim'] = self.output, self._loss_ssim
+            st['output'], st['loss_ssim'], st['loss_freq'] = self.output, self._loss_ssim, self._loss_freq
         else:
             st['lq'].copy_(self.lq, non_blocking=True)
             st['gt'].copy_(self.gt, non_blocking=True)
@@ -419,11 +450,12 @@ class RefGuidedImageCleanModel(BaseModel):
         else:
             red.allreduce_flat()
         st['gB'].replay()
-        self.output, self._loss_ssim = st['output'], st['loss_ssim']
+        self.output, self._loss_ssim, self._loss_freq = st['output'], st['loss_ssim'], st['loss_freq']
         return st['loss']
 
     skipped_steps = 0
     _loss_ssim = None       # the [1] loss tensor of train.ssim_opt's term of the last step (None without the block)
+    _loss_freq = None       # the same for train.freq_opt
 
     def get_current_log(self):
         """the base class's floats (a non-finite loss raises there); also the place where skipped optimiser steps become
