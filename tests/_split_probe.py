@@ -10,10 +10,14 @@ The bars come from the schemes, not from the kernels: tests/test_split_probe_hos
 and asserts that the full scheme stays under bar / 2 while every scheme with ONE product removed exceeds 8 * bar.
 
 A plain helper module (no fixtures): the input builders return (inputs, expected float64, mask of the non-zero outputs); where the mask
-is False the output has no non-zero term at all and must be exactly 0.0.  Everything here runs on the CPU.
+is False the output has no non-zero term at all and must be exactly 0.0.  Everything here runs on the CPU.  The builders of the fused
+NAFBlock chains (further down) return what their stage needs on top of that: where the operand of a stage is itself a product formed by
+the kernel, its place in the kernel's stored tensor and the weight row that multiplies it, so that the test forms the expectation from
+the stored value.
 
 Values: magnitudes uniform in [0.25, 4) with a random sign, full fp32 mantissas, for both operands -- inside the fp16 window, so one
 input set serves all three modes (randn would not: near-zero operands leave the window of the 2-way split)."""
+import functools
 import math
 
 import torch
@@ -256,6 +260,284 @@ def build_tok(P, N, Kd, seed=0, phase=0):
 
 def tok_phases(P, Kd):
     return -(-Kd // P)
+
+
+# ------------------------------------------------------------------ the fused NAFBlock chains (csrc/tdr_nafblock_chain.h)
+# Every GEMM stage of the chain kernels behind a one-hot operand.  The operands of the inner stages are formed inside the kernel, so they
+# are steered from the outside: the LayerNorm bias and the conv4 bias carry a chosen one-hot vector to conv1 / conv4 / conv5 of the forward
+# chains (lnw = 0 makes xn = lnb exactly, a zero tile makes t4 = b4 exactly); the saved tensors t4, y, mu, rs and lnw are plain inputs of the
+# backward chains.  Between the accumulator and the stored value only exact fp32 operations remain (+ 0, * 1, * 2^-k), so the bars are BAR[cls]
+# as they stand.  An expectation that is the same for every image and pixel has shape [1, M, 1, 1] (or [N, M, 1, 1]) and broadcasts.
+CHAIN_EPS = 1e-6
+WINDOW = (0.25, 4.0)
+
+
+def in_window(t):
+    """True when every non-zero element has its magnitude in the fp16 window [0.25, 4) of `values`"""
+    m = t.abs()[t != 0]
+    return bool(((m >= WINDOW[0]) & (m < WINDOW[1])).all())
+
+
+def pow2_toward_one(x):
+    """2^e with |x| 2^e in [2^-0.5, 2^0.5]: the factor that brings a product of two window values (1/16 ... 16) back into the window"""
+    return torch.pow(2.0, -torch.round(torch.log2(x.double().abs())))
+
+
+def values_with_product_in_window(w, seed):
+    """u with a full mantissa, |u| in the window and |w u| in the window as well, element by element (w in the window): magnitude uniform
+    in [max(1/4, 1/(4|w|)), min(4, 4/|w|)) shrunk by 1 % at both ends, random sign"""
+    g = torch.Generator().manual_seed(seed)
+    aw = w.double().abs()
+    lo, hi = torch.clamp(0.25 / aw, min=0.25) * 1.01, torch.clamp(4.0 / aw, max=4.0) * 0.99
+    mag = lo + (hi - lo) * torch.rand(w.shape, generator=g, dtype=torch.float64)
+    sign = torch.randint(0, 2, tuple(w.shape), generator=g).double() * 2 - 1
+    return (mag * sign).float()
+
+
+@functools.lru_cache(maxsize=None)
+def chain_image(N, C, H, W, seed):
+    """dense `values` [N, C, H, W], built once per shape and only read"""
+    return values(N, C, H, W, seed=seed)
+
+
+@functools.lru_cache(maxsize=None)
+def chain_weights(C, seed=40):
+    """conv1 / conv4 [2C, C, 1, 1], conv3 / conv5 / the TLSC channel attention [C, C, 1, 1]: dense `values`, built once and only read"""
+    return {'w1': values(2 * C, C, 1, 1, seed=seed), 'w3': values(C, C, 1, 1, seed=seed + 1), 'w4': values(2 * C, C, 1, 1, seed=seed + 2),
+            'w5': values(C, C, 1, 1, seed=seed + 3), 'wsca': values(C, C, 1, 1, seed=seed + 4)}
+
+
+def _mat(w):
+    return w.view(w.shape[0], w.shape[1]).double()
+
+
+def bias_route(C, k, seed=50):
+    """LayerNorm parameters that put v e_k in front of the GEMM behind the norm: lnw = 0, lnb = v[k] e_k -> (lnw, lnb, v[k])"""
+    v = values(C, seed=seed)
+    lnb = torch.zeros(C)
+    lnb[k] = v[k]
+    return torch.zeros(C), lnb, v[k]
+
+
+def mod_rows(N, C2, shift_only_upper=False):
+    """power-of-two modulation rows [N, C2] of the text-modulated chains: a = +-2^e, e = -1, 1, 2 with c mod 3, the sign alternating over channels and
+    images, b = +-2^(c mod 2) (shift_only_upper: b is a r on the upper half, r = 2^(c mod 2), and zero on the lower one -- a lower-half
+    shift would make every gate channel non-zero)"""
+    c = torch.arange(C2)
+    n = torch.arange(N)[:, None]
+    a = torch.pow(2.0, torch.tensor([-1.0, 1.0, 2.0])[c % 3])[None] * (1.0 - 2.0 * ((n + c[None]) % 2))
+    if not shift_only_upper:
+        return a, torch.pow(2.0, (c % 2).float())[None] * (1.0 - 2.0 * ((n + c[None] // 2) % 2))
+    b = a * torch.pow(2.0, (c % 2).float())[None]
+    b[:, :C2 // 2] = 0.0
+    return a, b
+
+
+def build_head_conv1(N, C, H, W, k, seed=0):
+    """naf_head_fwd, conv1 at K index k: xn = (x - mu) rstd 0 + lnb = v e_k at every pixel for any finite x, b1 = 0 ->
+    t1[o, p] = W1[o, k] v.  -> (inputs, expected [1, 2C, 1, 1], mask)"""
+    w1 = chain_weights(C)['w1']
+    lnw, lnb, v = bias_route(C, k)
+    inputs = {'x': chain_image(N, C, H, W, seed + 60), 'lnw': lnw, 'lnb': lnb, 'b1': torch.zeros(2 * C), 'w1': w1}
+    exp = (_mat(w1)[:, k] * v.double()).view(1, 2 * C, 1, 1)
+    return inputs, exp, torch.ones(1, 2 * C, 1, 1, dtype=torch.bool)
+
+
+def build_tail_conv4(N, C, H, W, k, seed=0):
+    """naf_tail_fwd, conv4 at K index k: g = 0 and b3 = 0 make y = x, the bias route on norm2 makes yn = v e_k, b4 = 0 ->
+    t4[o, p] = W4[o, k] v for all 2C rows.  -> (inputs, expected [1, 2C, 1, 1], mask)"""
+    wts = chain_weights(C)
+    lnw, lnb, v = bias_route(C, k)
+    z, one = torch.zeros(C), torch.ones(C)
+    inputs = {'g': torch.zeros(N, C, H, W), 'sca': torch.ones(N, C), 'x': chain_image(N, C, H, W, seed + 61), 'b3': z, 'beta': one, 'lnw': lnw,
+              'lnb': lnb, 'b4': torch.zeros(2 * C), 'b5': z, 'gamma': one, 'w3': wts['w3'], 'w4': wts['w4'], 'w5': wts['w5']}
+    exp = (_mat(wts['w4'])[:, k] * v.double()).view(1, 2 * C, 1, 1)
+    return inputs, exp, torch.ones(1, 2 * C, 1, 1, dtype=torch.bool)
+
+
+def build_tail_conv5(N, C, H, W, j, c_out=None, mod=False, seed=0):
+    """naf_tail_fwd, conv5 at K index j: x = 0, g = 0, b3 = 0, lnw = lnb = 0 make y = yn = 0 and t4 = b4 exactly (with the modulation rows
+    of dyn_tail_infer: t4 = b4 a2 + b2, powers of two times b4 and a sum of two equal powers of two -- exact, fused or not).  b4 is
+    non-zero at j and C + j, so the gate operand is one-hot at j with the value fl32(t4[j] t4[C + j]); one factor is a power of two, chosen so
+    that the product stays in the window.  b5 = 0, gamma = 1, y = 0: out[o, p] = W5[o, j] operand, rows below c_out.
+    -> (inputs with 't4' (the exact expected t4 rows [N, 2C]) and 'operand' [N], expected [N, c_out, 1, 1], mask)"""
+    c_out = C if c_out is None else c_out
+    wts = chain_weights(C)
+    a2, b2 = mod_rows(N, 2 * C, shift_only_upper=True) if mod else (torch.ones(N, 2 * C), torch.zeros(N, 2 * C))
+    v = values(C, seed=seed + 70)[j].double()
+    r = 2.0 ** (j % 2)
+    up = r * a2[:, C + j].double() + b2[:, C + j].double()                    # t4[C + j] per image: +-2^e, the same magnitude in every image
+    lo_scale = a2[:, j].double().abs() * up.abs()
+    assert (lo_scale == lo_scale[0]).all() and torch.log2(lo_scale[0]) % 1 == 0
+    adj = 1.0 if j % 2 == 0 else (2.0 if abs(v) < 2 else 0.5)                 # a non-trivial power of two that keeps |v| adj in the window
+    b4 = torch.zeros(2 * C)
+    b4[j], b4[C + j] = float(v * adj / lo_scale[0]), r
+    t4 = b4.double()[None] * a2.double() + b2.double()
+    assert torch.equal(t4.float().double(), t4)
+    gate = t4[:, :C].float() * t4[:, C:].float()                               # the IEEE product the kernel forms
+    assert torch.equal(gate.double(), t4[:, :C] * t4[:, C:]) and ((gate != 0).sum(1) == 1).all() and in_window(gate)
+    z, one = torch.zeros(C), torch.ones(C)
+    zimg = torch.zeros(N, C, H, W)
+    inputs = {'g': zimg, 'sca': torch.ones(N, C), 'x': zimg, 'b3': z, 'beta': one, 'lnw': z, 'lnb': z, 'b4': b4, 'b5': z, 'gamma': one,
+              'w3': wts['w3'], 'w4': wts['w4'], 'w5': wts['w5'], 'a2': a2, 'b2': b2, 't4': t4.float(), 'operand': gate[:, j]}
+    exp = _mat(wts['w5'])[None, :c_out, j] * gate[:, j].double()[:, None]
+    return inputs, exp.view(N, c_out, 1, 1), torch.ones(N, c_out, 1, 1, dtype=torch.bool)
+
+
+def build_tail_bwd_conv53(N, C, H, W, c_out=None, seed=0):
+    """naf_tail_bwd, conv5^T and conv3^T in one launch: dout one-hot over its c_out channels at every pixel, gamma = 1, t4 = 1 (both halves
+    of dt4 are W5^T dout), lnw = 0 with y = mu = 0 and rs = 1 (dy = (0 - 0 - 0) 1 + dout = dout on the first c_out rows, zero above),
+    beta = 1, sca = 1 (dgp = W3^T dy).  -> (inputs, {'dt4', 'dy', 'dgp': (expected, mask)})"""
+    c_out = C if c_out is None else c_out
+    wts = chain_weights(C)
+    dout = onehot_image(N, c_out, H, W, 'all', seed + 80)
+    inputs = {'dout': dout, 'gamma': torch.ones(C), 't4': torch.ones(N, 2 * C, H, W), 'y': torch.zeros(N, C, H, W), 'mu': torch.zeros(N, H * W),
+              'rs': torch.ones(N, H * W), 'lnw': torch.zeros(C), 'beta': torch.ones(C), 'sca': torch.ones(N, C),
+              'w5': wts['w5'][:c_out].contiguous(), 'w4': wts['w4'], 'w3': wts['w3']}
+    e5, m5 = expect_dgrad(dout, inputs['w5'], 1, 0, H, W)
+    e3, m3 = expect_dgrad(dout, wts['w3'][:c_out], 1, 0, H, W)
+    dy = torch.cat([dout, torch.zeros(N, C - c_out, H, W)], 1)
+    return inputs, {'dt4': (torch.cat([e5, e5], 1), torch.cat([m5, m5], 1)), 'dy': (dy.double(), dy != 0), 'dgp': (e3, m3)}
+
+
+PARTIAL_LAUNCHES = 16
+
+
+def partial_layout(N, C, H, W, launch):
+    """one (image, K index, pixel) per 64-pixel workgroup b of the launch: K index (16 (b + launch) + launch) mod 2C -- the sixteen
+    launches reach all 2C -- at pixel slot (4 launch + b) mod 64 of the workgroup -- all 64 slots occur.  -> (n, j, p) index vectors"""
+    assert H * W % 64 == 0 and (N * (H * W // 64)) * 16 == 2 * C
+    b = torch.arange(N * (H * W // 64))
+    j = (16 * (b + launch) + launch) % (2 * C)
+    return b // (H * W // 64), j, (b % (H * W // 64)) * 64 + (4 * launch + b) % 64
+
+
+def _ln_inputs(N, C, H, W, yhat, seed):
+    """(y, mu, rs) with (y - mu) rs = yhat exactly in fp32: mu is integer valued, y = mu + yhat, rs = 1"""
+    mu = torch.randint(-3, 4, (N, H * W), generator=torch.Generator().manual_seed(seed)).float()
+    return (mu.view(N, 1, H, W) + float(yhat)).expand(N, C, H, W).contiguous(), mu, torch.ones(N, H * W)
+
+
+def build_head_bwd_partials(N, C, H, W, launch, yhat=0, seed=0):
+    """naf_head_bwd, conv1^T (K = 2C) through the per-workgroup LayerNorm-gradient partials: dt1 is non-zero at one (channel j, pixel p*)
+    per workgroup (partial_layout), so its gb row sum_pixels dxn[c, p] is W1[j, c] dt1[j, p*] -- the other 63 terms are exact zeros -- and
+    its gw row is the same times yhat (0 or 1).  lnw = 0: dx = res.  -> (inputs, expected gb [workgroups, C], mask)"""
+    w1 = chain_weights(C)['w1']
+    n, j, p = partial_layout(N, C, H, W, launch)
+    val = values(n.numel(), seed=seed + 90 + launch)
+    dt1 = torch.zeros(N, 2 * C, H * W)
+    dt1[n, j, p] = val
+    y, mu, rs = _ln_inputs(N, C, H, W, yhat, seed + 91)
+    inputs = {'dt1': dt1.view(N, 2 * C, H, W), 'x': y, 'mu': mu, 'rs': rs, 'lnw': torch.zeros(C), 'res': chain_image(N, C, H, W, seed + 92), 'w1': w1}
+    exp = _mat(w1)[j] * val.double()[:, None]
+    return inputs, exp, torch.ones_like(exp, dtype=torch.bool)
+
+
+def build_tail_bwd_partials(N, C, H, W, launch, yhat=0, seed=0):
+    """naf_tail_bwd, conv4^T (K = 2C) through the partials: dout one-hot at every pixel, t4 non-zero at one (j, p*) per workgroup only, so
+    dt4 is non-zero only at ((j + C) mod 2C, p*), where it is (W5[o(p*), j mod C] dout[o(p*), p*]) t4[j, p*]; t4 there is the power of two that
+    brings that product into the window.  The gb row of the workgroup is W4[(j + C) mod 2C, c] times the kernel's own stored dt4 value.
+    -> (inputs, (n, j', p) of the operand, expected dt4 [N, 2C, H, W] with its mask, weight rows W4[j'] [workgroups, C] float64)"""
+    wts = chain_weights(C)
+    n, j, p = partial_layout(N, C, H, W, launch)
+    dout = onehot_image(N, C, H, W, 'all', seed + 100 + launch)
+    d = dout.view(N, C, H * W)
+    o = (d[n, :, p] != 0).float().argmax(1)
+    dg2 = _mat(wts['w5'])[o, j % C] * d[n, o, p].double()
+    t4 = torch.zeros(N, 2 * C, H * W)
+    sign = 1.0 - 2.0 * ((j + launch) % 2).double()
+    t4[n, j, p] = (pow2_toward_one(dg2) * sign).float()
+    jp = (j + C) % (2 * C)
+    edt4 = torch.zeros(N, 2 * C, H * W, dtype=torch.float64)
+    edt4[n, jp, p] = dg2 * t4[n, j, p].double()
+    y, mu, rs = _ln_inputs(N, C, H, W, yhat, seed + 101)
+    inputs = {'dout': dout, 'gamma': torch.ones(C), 't4': t4.view(N, 2 * C, H, W), 'y': y, 'mu': mu, 'rs': rs, 'lnw': torch.zeros(C),
+              'w5': wts['w5'], 'w4': wts['w4']}
+    edt4 = edt4.view(N, 2 * C, H, W)
+    return inputs, (n, jp, p), (edt4, edt4 != 0), _mat(wts['w4'])[jp]
+
+
+def dy_route_rows(C):
+    """the LayerNorm weight's hot row of each launch of the dy route: one per wave (32 rows), at a different place in each"""
+    return [32 * w + (11 * w + 5) % 32 for w in range(C // 32)]
+
+
+def build_head_bwd_dy(N, C, H, W, k, seed=0):
+    """naf_head_bwd, conv1^T at EVERY pixel through dx: dt1 one-hot over its 2C channels at every pixel, lnw = e_k, x = mu (yhat = 0), rs = 1,
+    res = 0.  Then g = dxn lnw is dxn[k] at row k and zero elsewhere, mean_c(g yhat) = 0, mean_c(g) = dxn[k, p] / C (one non-zero term, a
+    power-of-two scaling), and for every row c != k: dx[c, p] = (0 - 0 - dxn[k, p] / C) 1 + 0 = -W1[j(p), k] dt1[j(p), p] / C.
+    -> (inputs, expected [N, 1, H, W], mask [N, C, H, W]: every row but k)"""
+    w1 = chain_weights(C)['w1']
+    dt1 = onehot_image(N, 2 * C, H, W, 'all', seed + 110 + k)
+    y, mu, rs = _ln_inputs(N, C, H, W, 0, seed + 111)
+    lnw = torch.zeros(C)
+    lnw[k] = 1.0
+    inputs = {'dt1': dt1, 'x': y, 'mu': mu, 'rs': rs, 'lnw': lnw, 'res': torch.zeros(N, C, H, W), 'w1': w1}
+    dxn, m = expect_dgrad(dt1, w1, 1, 0, H, W)
+    assert m.all()
+    mask = torch.ones(N, C, H, W, dtype=torch.bool)
+    mask[:, k] = False
+    return inputs, -dxn[:, k:k + 1] / C, mask
+
+
+def build_tail_bwd_dy(N, C, H, W, k, seed=0):
+    """naf_tail_bwd, conv4^T at EVERY pixel through dy: dout one-hot (channel o(p)) and t4 non-zero at one channel j(p) of its 2C per pixel --
+    a power of two, as in build_tail_bwd_partials -- so dt4 is one-hot at j'(p) = (j(p) + C) mod 2C; lnw = e_k, y = mu, rs = 1.  The skip
+    gradient of the tail is dout itself, so dy[c, p] = -W4[j'(p), k] dt4[j'(p), p] / C on every row c outside {k, o(p)} (row o(p) adds dout with
+    a rounding and is left out; the pixels all stay).
+    -> (inputs, (n, j', p) of the operands, expected dt4 with its mask, W4[j'(p), k] [N, 1, H, W] float64, mask of the rows)"""
+    wts = chain_weights(C)
+    HW = H * W
+    dout = onehot_image(N, C, H, W, 'all', seed + 120 + k)
+    d = dout.view(N, C, HW)
+    n = torch.arange(N).repeat_interleave(HW)
+    p = torch.arange(HW).repeat(N)
+    o = (d != 0).float().argmax(1).reshape(-1)
+    j = (7 * p + n + 3 * k) % (2 * C)
+    dg2 = _mat(wts['w5'])[o, j % C] * d[n, o, p].double()
+    t4 = torch.zeros(N, 2 * C, HW)
+    t4[n, j, p] = (pow2_toward_one(dg2) * (1.0 - 2.0 * ((p + n) % 2).double())).float()
+    jp = (j + C) % (2 * C)
+    edt4 = torch.zeros(N, 2 * C, HW, dtype=torch.float64)
+    edt4[n, jp, p] = dg2 * t4[n, j, p].double()
+    y, mu, rs = _ln_inputs(N, C, H, W, 0, seed + 121)
+    lnw = torch.zeros(C)
+    lnw[k] = 1.0
+    inputs = {'dout': dout, 'gamma': torch.ones(C), 't4': t4.view(N, 2 * C, H, W), 'y': y, 'mu': mu, 'rs': rs, 'lnw': lnw, 'w5': wts['w5'],
+              'w4': wts['w4']}
+    mask = dout == 0
+    mask[:, k] = False
+    edt4 = edt4.view(N, 2 * C, H, W)
+    return inputs, (n, jp, p), (edt4, edt4 != 0), _mat(wts['w4'])[jp, k].view(N, 1, H, W), mask
+
+
+def build_local_stages(N, C, H, W, seed=0):
+    """naf_tail_infer_local with gamma = 0 (out = y): the conv3 stage alone -- pooled = 0 and bsca = 1 make the attention map 1.0, g is
+    one-hot, y = W3 g -- and the wsca stage in front of it -- pooled one-hot (channel c(p), value u), bsca = 0, g = 1.0 at ONE channel h(p), so
+    that conv3's operand is the single product s = Wsca[h(p), c(p)] u there and y[o, p] = W3[o, h(p)] s: two single products in a chain, u drawn
+    with a full mantissa so that u and Wsca[h, c] u both stay in the window.  -> {'conv3' | 'wsca': (inputs, expected y, mask)}"""
+    wts = chain_weights(C)
+    zimg, z, one = torch.zeros(N, C, H, W), torch.zeros(C), torch.ones(C)
+    # (lnw = lnb = 0 and b4 = 0: conv4 and conv5 run on zero operands, so that out = (0 + 0) 0 + y whatever the range of y)
+    common = {'x': zimg, 'b3': z, 'beta': one, 'lnw': z, 'lnb': z, 'b4': torch.zeros(2 * C), 'b5': z, 'gamma': z, 'w3': wts['w3'], 'w4': wts['w4'],
+              'w5': wts['w5'], 'wsca': wts['wsca']}
+    g = onehot_image(N, C, H, W, 'all', seed + 130)
+    e3, m3 = expect_conv(g, wts['w3'])
+    conv3 = (dict(common, g=g, pooled=zimg, bsca=one), e3, m3)
+    HW = H * W
+    n = torch.arange(N).repeat_interleave(HW)
+    p = torch.arange(HW).repeat(N)
+    c, h = (7 * p + n) % C, (11 * p + 5 * n + 3) % C
+    ws = _mat(wts['wsca'])[h, c]
+    u = values_with_product_in_window(ws, seed + 131)
+    pooled, gh = torch.zeros(N, C, HW), torch.zeros(N, C, HW)
+    pooled[n, c, p] = u
+    gh[n, h, p] = 1.0
+    s = (ws * u.double()).view(N, HW)
+    assert in_window(u) and in_window(s)
+    exp = (_mat(wts['w3'])[:, h].t().reshape(N, HW, C).permute(0, 2, 1) * s[:, None]).reshape(N, C, H, W)
+    wsca = (dict(common, g=gh.view(N, C, H, W), pooled=pooled.view(N, C, H, W), bsca=z), exp, torch.ones(N, C, H, W, dtype=torch.bool))
+    return {'conv3': conv3, 'wsca': wsca}
 
 
 def coverage(masks):

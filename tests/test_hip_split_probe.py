@@ -10,9 +10,12 @@ The bar of a launch is that of the arithmetic it is documented to run (DESIGN §
 gradients outside a loss-scaled pass (kernels.GRAD_SCALED off) stay on the bf16 triples and are pinned at the bx3 bar, inside one at the
 hx2 bar; conv_wgrad 1x1 with kernels.WGRAD_1X1_BX3 off is the exact kernel in every mode and is pinned at the f32 bar.
 
-Left out, and why: tok16_gemm (a single fp16 product by design); conv1 / conv4 / conv5 of the fused NAFBlock chains and the GEMMs of the
-backward chains (their operands are LayerNorm / gate outputs formed inside the kernel and cannot be made one-hot: they stay with
-tests/test_hip_nafblock_fused.py and the chain tests); the dilated search convolutions (packed math='f32': exact by construction).
+The fused NAFBlock chains: their conv3 stage is probed here through the saved tensor y (test_chain_conv3_stage); every other GEMM stage
+-- conv1, conv4, conv5, the data gradients conv5^T, conv4^T, conv3^T, conv1^T of the backward chains, the forward-only and text-modulated
+twins and the channel-attention GEMM of the TLSC tail -- is probed in tests/test_hip_chain_probe.py.  Their operands are formed inside the
+kernel, so they are steered from the outside: the LayerNorm bias (lnw = 0, lnb = v e_k) and the conv4 bias place a one-hot vector in front of
+the forward stages, and the saved tensors t4, y, mu, rs are plain inputs of the backward chains.
+Left out, and why: tok16_gemm (a single fp16 product by design); the dilated search convolutions (packed math='f32': exact by construction).
 wgrad1x1_group takes problems of ONE shape per launch, so its three problems differ in their data, not in C."""
 import contextlib
 import functools
@@ -295,8 +298,8 @@ def test_tok16x2_gemm(shape):
 def test_chain_conv3_stage(mode, shape):
     """kernels.naf_tail_fwd with a one-hot gate output g, channel attention 1.0, beta 1.0, a zero conv3 bias and a zero block input: the
     saved tensor y = (W3 (g * sca) + b3) * beta + x is W3 g, one product per element.  HW = 64 * (C / 16) and N = 2: every value of the
-    per-workgroup group rotation of gemm_split occurs.  conv4 / conv5 of the same launch (and conv1 of the head chain) read LayerNorm /
-    gate outputs and cannot be made one-hot: they stay with the existing chain tests."""
+    per-workgroup group rotation of gemm_split occurs.  conv4 / conv5 of the same launch, conv1 of the head chain and the backward chains:
+    tests/test_hip_chain_probe.py."""
     N, C, H, W = shape
     (g, w3), exp, mask = conv_case((N, C, C, H, W, 1, 1, 0))
     r = lambda *s, seed: torch.randn(*s, generator=torch.Generator().manual_seed(seed)).cuda()

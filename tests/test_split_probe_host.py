@@ -4,7 +4,10 @@ CPU, stays under bar / 2; the same list with any ONE product removed exceeds 8 *
 kernel without this file failing).  Per builder and per shape that tests/test_hip_split_probe.py runs: `expected` equals a dense float64
 convolution / einsum of the same inputs to 1e-15 relative, outputs outside the mask are exact zeros of that dense result, and at least
 90 % of all outputs are single products (over the launches of a case where one launch cannot reach them all: stride-2 data and weight
-gradients, K longer than the token count) -- the rest are the exact-zero border outputs.
+gradients, K longer than the token count) -- the rest are the exact-zero border outputs.  Per builder of the fused NAFBlock chains
+(tests/test_hip_chain_probe.py): a float64 model of the chain gives the expected single product where the mask is set and exact zeros
+elsewhere; the launches of a case together reach every K index, every output row and all 64 pixel slots of a workgroup; and the schemes
+keep bar / 2 and 8 * bar on the operand distributions of those probes, the product-valued operands (gate, dt4, attention map) included.
 
 The sample set is fixed.  For hx2 the maximum over 2^20 pairs depends on the draw: eight draws gave 4.5e-7 ... 4.9e-7 around bar / 2 =
 4.77e-7 (this one: 4.56e-7), and the scheme's analytic worst case is the dropped mm term 2^-22 plus one rounding of each residual plane
@@ -143,3 +146,202 @@ def test_chain_layout_reaches_every_channel_in_every_workgroup_rotation(shape):
     (g, w), exp, mask = SP.build_conv(N, C, C, H, W, 1, seed=11)
     assert mask.all() and ((g != 0).sum((2, 3)) > 0).all()
     _close(exp, F.conv2d(g.double(), w.double()), mask)
+
+
+# ------------------------------------------------------------------ the fused NAFBlock chains: float64 models of the kernels' stages
+# (csrc/tdr_nafblock_chain.h, plain torch; the builders' expectations must come out of them exactly -- sums whose other terms are exact
+# zeros, products of two 24-bit values and power-of-two scalings are all exact in float64 -- or to 1e-15 where a 48-bit product is an operand)
+CS = SP.CHAIN_SHAPES
+cid = lambda s: 'x'.join(map(str, s))
+
+
+def _mm(w, x):
+    return torch.einsum('oc,nchw->nohw', w.view(w.shape[0], w.shape[1]).double(), x.double())
+
+
+def _mmt(w, d):
+    return torch.einsum('oc,nohw->nchw', w.view(w.shape[0], w.shape[1]).double(), d.double())
+
+
+def _vec(v):
+    return v.double().view(1, -1, 1, 1)
+
+
+def _ln(y, lnw, lnb):
+    mu = y.mean(1, keepdim=True)
+    return (y - mu) / torch.sqrt(((y - mu) ** 2).mean(1, keepdim=True) + SP.CHAIN_EPS) * _vec(lnw) + _vec(lnb)
+
+
+def model_tail_fwd(i, c_out, mod=False):
+    C = i['g'].shape[1]
+    y = i['x'].double() + (_mm(i['w3'], i['g'].double() * i['sca'].double()[:, :, None, None]) + _vec(i['b3'])) * _vec(i['beta'])
+    yn = _ln(y, i['lnw'], i['lnb'])
+    t4 = _mm(i['w4'], yn) + _vec(i['b4'])
+    if mod:
+        t4 = t4 * i['a2'].double()[:, :, None, None] + i['b2'].double()[:, :, None, None]
+    gate = t4[:, :C] * t4[:, C:]
+    out = y[:, :c_out] + (_mm(i['w5'][:c_out], gate) + _vec(i['b5'][:c_out])) * _vec(i['gamma'][:c_out])
+    return y, yn, t4, gate, out
+
+
+def model_bwd(dt, w, y, mu, rs, lnw, res):
+    """the K = 2C data gradient + LayerNorm backward + skip -> (dyn, dy, gw partials, gb partials [workgroups, C])"""
+    N, C, H, W = y.shape
+    dyn = _mmt(w, dt)
+    yhat = (y.double() - mu.double().view(N, 1, H, W)) * rs.double().view(N, 1, H, W)
+    g = dyn * _vec(lnw)
+    dy = (g - yhat * (g * yhat).sum(1, keepdim=True) / C - g.sum(1, keepdim=True) / C) * rs.double().view(N, 1, H, W) + res.double()
+    parts = lambda t: t.reshape(N, C, H * W // 64, 64).sum(-1).permute(0, 2, 1).reshape(-1, C)
+    return dyn, dy, parts(dyn * yhat), parts(dyn)
+
+
+def model_tail_bwd(i, c_out):
+    N, C, H, W = i['y'].shape
+    dg2 = _mmt(i['w5'][:c_out], i['dout'].double() * _vec(i['gamma'][:c_out]))
+    t4 = i['t4'].double()
+    dt4 = torch.cat([dg2 * t4[:, C:], dg2 * t4[:, :C]], 1)
+    res = torch.cat([i['dout'].double(), torch.zeros(N, C - c_out, H, W, dtype=torch.float64)], 1)
+    return (dt4,) + model_bwd(dt4, i['w4'], i['y'], i['mu'], i['rs'], i['lnw'], res)
+
+
+def _some(C):
+    """K indices of the forward loops that the dense float64 model is run on (all of them are checked for their one-hot layout)"""
+    return sorted(set(range(0, C, max(1, C // 8))) | {1, C // 2 - 1, C - 1})
+
+
+def _exact(got, exp, mask=None):
+    exp = exp.expand_as(got)
+    assert torch.equal(got, exp)
+    if mask is not None:
+        assert (exp[~mask.expand_as(got)] == 0).all() and (exp[mask.expand_as(got)] != 0).all()
+
+
+@pytest.mark.parametrize('shape', CS, ids=cid)
+def test_chain_forward_builders_equal_the_float64_chain(shape):
+    N, C, H, W = shape
+    for k in range(C):                                                            # every K index has its launch, operands in the window
+        for build in (SP.build_head_conv1, SP.build_tail_conv4):
+            inp, exp, mask = build(N, C, H, W, k)
+            assert inp['lnb'].nonzero().view(-1).tolist() == [k] and not inp['lnw'].any() and SP.in_window(inp['lnb'])
+            assert mask.all() and exp.shape == (1, 2 * C, 1, 1) and (exp != 0).all()      # every output row, the same at every pixel
+        for mod in (False, True):
+            inp, exp, mask = SP.build_tail_conv5(N, C, H, W, k, mod=mod)
+            assert inp['b4'].nonzero().view(-1).tolist() == [k, C + k] and mask.all() and (exp != 0).all() and SP.in_window(inp['operand'])
+            assert not inp['b2'][:, :C].any() and (mod == bool(inp['b2'][:, C:].all())) and (mod == bool((inp['a2'] != 1).all()))
+    for k in _some(C):
+        inp, exp, mask = SP.build_head_conv1(N, C, H, W, k)
+        for a, b in ((torch.ones(N, C), torch.zeros(N, C)), SP.mod_rows(N, C)):     # the modulated head: LayerNorm of x a + b
+            xn = _ln(inp['x'].double() * a.double()[:, :, None, None] + b.double()[:, :, None, None], inp['lnw'], inp['lnb'])
+            _exact(xn, _vec(inp['lnb']))
+            _exact(_mm(inp['w1'], xn) + _vec(inp['b1']), exp, mask)
+        inp, exp, mask = SP.build_tail_conv4(N, C, H, W, k)
+        y, yn, t4, gate, out = model_tail_fwd(inp, C)
+        _exact(y, inp['x'].double())
+        _exact(yn, _vec(inp['lnb']))
+        _exact(t4, exp, mask)
+        for mod in (False, True):
+            for c_out in (C, C // 2):
+                inp, exp, mask = SP.build_tail_conv5(N, C, H, W, k, c_out=c_out, mod=mod)
+                y, yn, t4, gate, out = model_tail_fwd(inp, c_out, mod)
+                assert not y.any() and not yn.any()
+                _exact(t4, inp['t4'].double()[:, :, None, None])
+                assert torch.equal(gate[:, k, 0, 0], inp['operand'].double()) and (gate.sum(1) == gate[:, k]).all()
+                _exact(out, exp, mask)
+
+
+@pytest.mark.parametrize('shape', CS, ids=cid)
+def test_chain_backward_conv5t_conv3t_builder_equals_the_float64_chain(shape):
+    N, C, H, W = shape
+    for c_out in (C, C // 2):
+        inp, exp = SP.build_tail_bwd_conv53(N, C, H, W, c_out)
+        assert ((inp['dout'] != 0).sum(1) == 1).all() and ((inp['dout'] != 0).sum((0, 2, 3)) > 0).all()      # every pixel, every K index
+        dt4, dyn, dy, gw, gb = model_tail_bwd(inp, c_out)
+        _close(exp['dt4'][0], dt4, exp['dt4'][1])
+        assert exp['dt4'][1].all()
+        assert torch.equal(dy, exp['dy'][0])
+        _close(exp['dgp'][0], _mmt(inp['w3'], dy * _vec(inp['beta'])) * inp['sca'].double()[:, :, None, None], exp['dgp'][1])
+        assert exp['dgp'][1].all()
+
+
+@pytest.mark.parametrize('shape', CS, ids=cid)
+def test_chain_partial_builders_equal_the_float64_chain_and_reach_everything(shape):
+    N, C, H, W = shape
+    ks, slots = set(), set()
+    for launch, yhat in [(l, 0) for l in range(SP.PARTIAL_LAUNCHES)] + [(0, 1)]:
+        n, j, p = SP.partial_layout(N, C, H, W, launch)
+        assert torch.equal(n * (H * W // 64) + p // 64, torch.arange(n.numel()))      # one operand in every workgroup
+        ks |= set(j.tolist())
+        slots |= set((p % 64).tolist())
+        # head
+        inp, exp, mask = SP.build_head_bwd_partials(N, C, H, W, launch, yhat)
+        assert int((inp['dt1'] != 0).sum()) == n.numel() and SP.in_window(inp['dt1']) and mask.all() and exp.shape == (n.numel(), C)
+        dyn, dy, gw, gb = model_bwd(inp['dt1'], inp['w1'], inp['x'], inp['mu'], inp['rs'], inp['lnw'], inp['res'])
+        assert torch.equal(gb, exp) and torch.equal(gw, gb * yhat) and torch.equal(dy, inp['res'].double()) and (exp != 0).all()
+        # tail
+        inp, (n2, jp, p2), (edt4, mdt4), w4rows = SP.build_tail_bwd_partials(N, C, H, W, launch, yhat)
+        assert torch.equal(n2, n) and torch.equal(p2, p) and torch.equal(jp, (j + C) % (2 * C))
+        dt4, dyn, dy, gw, gb = model_tail_bwd(inp, C)
+        assert torch.equal(dt4, edt4) and int(mdt4.sum()) == n.numel()
+        op = edt4.view(N, 2 * C, H * W)[n, jp, p]
+        assert SP.in_window(op.float()) and (op != 0).all()
+        ref = w4rows * op[:, None]
+        assert ((gb - ref).abs() / ref.abs()).max().item() <= 1e-15 and torch.equal(gw, gb * yhat) and torch.equal(dy, inp['dout'].double())
+    assert ks == set(range(2 * C)) and slots == set(range(64))                      # every K index (and with C + .: every row of W4), every slot
+
+
+@pytest.mark.parametrize('shape', CS, ids=cid)
+def test_chain_dy_route_builders_equal_the_float64_chain_and_reach_everything(shape):
+    N, C, H, W = shape
+    rows = SP.dy_route_rows(C)
+    assert sorted(k // 32 for k in rows) == list(range(C // 32)) and len({k % 32 for k in rows}) == len(rows)      # one row per wave
+    for k in rows:
+        inp, exp, mask = SP.build_head_bwd_dy(N, C, H, W, k)
+        hot = inp['dt1'] != 0
+        assert (hot.sum(1) == 1).all() and (hot.sum((2, 3)) > 0).all() and int((~mask).sum()) == N * H * W      # every pixel; all 2C per image
+        dyn, dy, gw, gb = model_bwd(inp['dt1'], inp['w1'], inp['x'], inp['mu'], inp['rs'], inp['lnw'], inp['res'])
+        assert torch.equal(dy[mask.expand_as(dy)], exp.expand_as(dy)[mask]) and (exp != 0).all()
+        inp, (n, jp, p), (edt4, mdt4), w4col, mask = SP.build_tail_bwd_dy(N, C, H, W, k)
+        dt4, dyn, dy, gw, gb = model_tail_bwd(inp, C)
+        assert torch.equal(dt4, edt4) and (mdt4.sum(1) == 1).all() and (mdt4.sum((2, 3)) > 0).all()               # one-hot at every pixel, all 2C
+        op = edt4.view(N, 2 * C, H * W)[n, jp, p].view(N, 1, H, W)
+        assert SP.in_window(op.float()) and int((~mask).sum()) == 2 * N * H * W - int((inp['dout'][:, k] != 0).sum())
+        ref = (-w4col * op / C).expand_as(dy)
+        assert ((dy - ref).abs()[mask] / ref.abs()[mask]).max().item() <= 1e-15
+
+
+@pytest.mark.parametrize('shape', CS, ids=cid)
+def test_chain_local_builders_equal_the_float64_chain(shape):
+    N, C, H, W = shape
+    for stage, (inp, exp, mask) in SP.build_local_stages(N, C, H, W).items():
+        s = _mm(inp['wsca'], inp['pooled']) + _vec(inp['bsca'])
+        y, yn, t4, gate, out = model_tail_fwd(dict(inp, g=inp['g'].double() * s, sca=torch.ones(N, C)), C)
+        assert mask.all() and not yn.any() and not gate.any() and torch.equal(out, y)
+        hot = (inp['g'] if stage == 'conv3' else inp['pooled']) != 0
+        assert (hot.sum(1) == 1).all() and (hot.sum((2, 3)) > 0).all()
+        _close(exp, y, mask)
+
+
+def _operand_distributions():
+    """(name, a, b, bars) of the chain probes' products beyond `values` x `values`: the product-valued operands"""
+    n = 1 << 18
+    w, v, d = SP.values(n, seed=400), SP.values(n, seed=401), SP.values(n, seed=402)
+    adj = torch.where(torch.arange(n) % 2 == 0, torch.ones(n), torch.where(v.abs() < 2, torch.full((n,), 2.0), torch.full((n,), 0.5)))
+    yield 'conv5: W5 x gate (v 2^e)', w, v * adj
+    for scheme in ('bx3', 'hx2'):
+        prod = SP.emulate(SP.values(n, seed=403), d, scheme)
+        yield f'conv4^T: W4 x dt4 ({scheme} product 2^e)', w, prod * SP.pow2_toward_one(prod).float()
+    u = SP.values_with_product_in_window(w, 404)
+    yield 'wsca: Wsca x pooled', w, u
+    for scheme in ('bx3', 'hx2'):
+        yield f'conv3 behind wsca: W3 x s ({scheme} product)', SP.values(n, seed=405), SP.emulate(w, u, scheme)
+
+
+@pytest.mark.parametrize('scheme', ['bx3', 'hx2'])
+def test_chain_operand_distributions_keep_the_bars_sharp(scheme):
+    for name, a, b in _operand_distributions():
+        assert SP.in_window(a) and SP.in_window(b), name
+        worst = _rel(SP.emulate(a, b, scheme), a, b).max().item()
+        print(f'emulated {scheme} on {name}: max rel {worst:.2e} (bar {SP.BAR[scheme]:.2e})')
+        assert worst <= SP.BAR[scheme] / 2, name
+        for drop in SP.PRODUCTS[scheme]:
+            assert _rel(SP.emulate(a, b, scheme, drop=drop), a, b).max().item() >= 8 * SP.BAR[scheme], (name, drop)
