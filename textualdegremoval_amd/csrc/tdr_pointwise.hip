@@ -962,7 +962,9 @@ extern "C" int tdr_layernorm2d_bwd(const float* go, const float* x, int64_t x_ns
 __global__ __launch_bounds__(256) void pair_fold_partials_kernel(const float* __restrict__ part, int nparts, int C2,
                                                                 float* __restrict__ mid) {
     __shared__ float red[256];
-    const int SL = C2 >= 256 ? 1 : 256 / C2;                 // (C2 is a power of two below 256 on this path, or >= 256)
+    // any C2: below 256 the SL = floor(256 / C2) slices take SL * C2 threads, the rest of the block idles (`sl < SL` below: C2 = 96,
+    // Restormer's C = 48, runs 2 slices on 192 threads; C2 in 129 .. 255 one slice, like the column layout of C2 >= 256)
+    const int SL = C2 >= 256 ? 1 : 256 / C2;
     const int el = SL > 1 ? (int)threadIdx.x % C2 : (int)threadIdx.x, sl = SL > 1 ? (int)threadIdx.x / C2 : 0;
     const int e = SL > 1 ? el : blockIdx.x * 256 + el;       // element of the [2][C] row
     const bool live = e < C2 && sl < SL;
